@@ -12,9 +12,14 @@ A "step" is one pass of the hot path over one batch of synthetic clouds already 
 DGCNN(emb_dims=1024).eval() forward on x[32,1024,3] (fused kNN -> fused EdgeConv stack -> conv5 GEMM,
 all hand-written HIP) followed by ChamferDistanceLoss()(a[32,1024,3], b[32,1024,3]) including, for
 N>1, the all_gather of the per-shard loss partial sums (weak scaling: 32 clouds per GPU).
-Rank 0 prints ONE JSON line (contract in the task statement) carrying `roofline` (dominant kernel:
-the EdgeConv MFMA kernel; live HIP-event timing) and `cpu_baseline` (the reference's own CPU
-op sequence -- matmul/topk kNN, torch convs, torch-fallback Chamfer -- on this box's host cores, on rank 0's tensors; N=1 only).
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run does only what that line's headline
+(`value`, `ms_per_step`) needs: set-up, warm-up, the K timed steps, `--dump-outputs` if given, the line.
+With --full the line also carries `roofline` (dominant kernel: the EdgeConv MFMA kernel; live HIP-event timing),
+`roofline_knn`, `kernels`, the other loss-exchange mode (N>1), `other_configs` and `cpu_baseline` (the reference's own
+CPU op sequence -- matmul/topk kNN, torch convs, torch-fallback Chamfer -- on the host's cores, on rank 0's tensors; N=1 only).
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, for comparing two builds output for
+output on the same seeded inputs.
 """
 import argparse
 import json
@@ -45,6 +50,33 @@ KNN_BYTES_PER_CLOUD = NPTS * 3 * 4 + NPTS * KNN * 8                 # 176 128 B
 CHAMFER_BYTES_PER_CLOUD = 2 * NPTS * 3 * 4 + 2 * NPTS * (4 + 4)     # 40 960 B
 EDGECONV_FLOP_PER_CLOUD = NPTS * KNN * 2 * (6 * 64 + 64 * 64 + 64 * 128 + 128 * 256)
 CONV5_FLOP_PER_CLOUD = NPTS * 2 * 512 * EMB
+# --dump-outputs: the c2 step's features are [32, 1024, 1024] fp32 = 128 MB, so a fixed sample of them is written
+FEAT_SAMPLE, FEAT_SAMPLE_SEED = 1 << 22, 0
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """arrays: name -> numpy array (float32 or float64), written as dirname/<name>.npy"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"[bench] --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def feature_sample(feat):
+    """FEAT_SAMPLE values of the step's features at fixed positions (same positions in every run), as float32"""
+    import numpy as np
+    pos = np.sort(np.random.default_rng(FEAT_SAMPLE_SEED).choice(feat.numel(), size=min(FEAT_SAMPLE, feat.numel()), replace=False))
+    return feat.reshape(-1)[torch.from_numpy(pos).to(feat.device)].float().cpu().numpy()
+
+
+def loss_array(loss):
+    import numpy as np
+    return np.array([float(loss)], dtype=np.float64)
 
 
 def flush_c_stdio():
@@ -331,7 +363,7 @@ def other_configs(dev, iters=10, warm=3):
         c5 = {}
         for tag, extra in (("pipelined", []), ("serial", ["--c5-serial"])):
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "c5", "--gpus", "1", "--steps", "40", "--warmup", "10",
-                                "--no-cpu-baseline", "--no-other-configs"] + extra, capture_output=True, text=True, timeout=240)
+                                "--full", "--no-cpu-baseline", "--no-other-configs"] + extra, capture_output=True, text=True, timeout=240)
             line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
             if r.returncode == 0 and line:
                 j = json.loads(line[-1])
@@ -660,30 +692,34 @@ def main_c5(args, rank, world, local, dev, dist, parallel):
 
     sync()
     t0 = time.perf_counter()
-    digest_v = None
+    feat_v = digest_v = None
     for i in range(args.steps):
-        _, digest_v = step()
+        feat_v, digest_v = step()
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"set_abstraction_features": feat_v.float().cpu().numpy(),
+                                         "digest": digest_v.double().cpu().numpy()})
 
-    # untimed: the kernels' own durations (HIP events around the stages of a few SERIAL eager steps on one stream) and the
-    # serial step itself (sampling, then the rest, back to back: one batch's latency)
-    timer = _fused.StageTimer(only=("group_kernel", "fps", "ball_query", "mlp"))
-    _fused.TIMER = timer
-    for c in (0, 1, 0, 1):
-        compute_serial(c)
-    torch.cuda.synchronize()
-    _fused.TIMER = None
-    stage_ms = timer.mean_ms()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for c in (0, 1):
-        compute_serial(c)
-    e0.record()
-    for c in (0, 1) * 5:
-        compute_serial(c)
-    e1.record()
-    torch.cuda.synchronize()
-    serial_ms = e0.elapsed_time(e1) / 10
+    if args.full:
+        # --full, untimed: the kernels' own durations (HIP events around the stages of a few SERIAL eager steps on one stream) and the
+        # serial step itself (sampling, then the rest, back to back: one batch's latency)
+        timer = _fused.StageTimer(only=("group_kernel", "fps", "ball_query", "mlp"))
+        _fused.TIMER = timer
+        for c in (0, 1, 0, 1):
+            compute_serial(c)
+        torch.cuda.synchronize()
+        _fused.TIMER = None
+        stage_ms = timer.mean_ms()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for c in (0, 1):
+            compute_serial(c)
+        e0.record()
+        for c in (0, 1) * 5:
+            compute_serial(c)
+        e1.record()
+        torch.cuda.synchronize()
+        serial_ms = e0.elapsed_time(e1) / 10
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     per_rank = [t.clone() for _ in range(world)]
@@ -692,25 +728,6 @@ def main_c5(args, rank, world, local, dev, dist, parallel):
     per_rank = torch.stack(per_rank).cpu()
     elapsed = float(per_rank[:, 0].max())
     if rank == 0:
-        fused = "group_kernel" not in stage_ms          # sa_fused.hip: gather + three layers + max in one launch (the "mlp" stage)
-        mlp_tf = B_PER_GPU * C5_MLP_FLOP_PER_CLOUD / (stage_ms["mlp"] * 1e-3) / 1e12 if stage_ms.get("mlp") else None
-        if fused:
-            roof = {"kernel": "sa_mlp3_kernel<8,32,32,64,2>", "bound": "mfma", "achieved": mlp_tf, "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s",
-                    "frac": mlp_tf / MFMA_F32_PEAK_TF if mlp_tf else None, "traffic": pmc_traffic("sa_mlp3"), "traffic_source": pmc_source("sa_mlp3"),
-                    "avg_launch_ms": stage_ms.get("mlp"), "algorithmic_flop_per_launch": B_PER_GPU * C5_MLP_FLOP_PER_CLOUD,
-                    # indices in, six gathered values per (centroid, neighbour), 64 maxima per centroid out
-                    "algorithmic_bytes_per_launch": B_PER_GPU * (C5_S * C5_K * 4 + C5_S * C5_K * 6 * 4 + 64 * C5_S * 4),
-                    "note": "the set-abstraction layer behind the ball query as one kernel (gather, 6 -> 32 -> 32 -> 64 on the fp32 MFMA, max over "
-                            "K): exact fp32 fma chains, priced against the fp32 matrix peak; the step itself is bound by furthest point "
-                            "sampling's 1024 dependent rounds (one workgroup per cloud) packed beside it, see kernels.fps_ms and config.pipeline"}
-        else:
-            grp_ms = stage_ms["group_kernel"]
-            grp_gbs = B_PER_GPU * C5_GROUP_BYTES_PER_CLOUD / (grp_ms * 1e-3) / 1e9
-            roof = {"kernel": "group_concat_kernel", "bound": "hbm", "achieved": grp_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": grp_gbs / HBM_PEAK_GBS, "traffic": pmc_traffic("group_c5"), "traffic_source": pmc_source("group_c5"),
-                    "avg_launch_ms": grp_ms, "algorithmic_bytes_per_launch": B_PER_GPU * C5_GROUP_BYTES_PER_CLOUD,
-                    "note": "microseconds of the step: the step is bound by furthest point sampling's 1024 dependent rounds "
-                            "(latency, one workgroup per cloud), see kernels.fps_ms"}
         out = {
             "metric": "clouds/sec FlowNet3D sa1 set-conv (FPS + ball query + grouping + shared MLP) B=32 per GPU N=8192 -- BASELINE configs[4], "
                       "NOT the headline metric (that is the default --workload c2 line)",
@@ -733,15 +750,37 @@ def main_c5(args, rank, world, local, dev, dist, parallel):
             "per_rank_ms_per_step": [float(v) / args.steps * 1e3 for v in per_rank[:, 0]],
             "rank0_placement": getattr(args, "placement", None),
             "multi_gpu_note": "no N > 1 number has been measured by the builder in any round (a gpurun box has one GPU)",
-            "serial_ms_per_step": serial_ms,
-            "roofline": roof,
-            "kernels": {"fps_ms": stage_ms.get("fps"), "ball_query_ms": stage_ms.get("ball_query"), "group_ms": stage_ms.get("group_kernel"),
-                        "mlp_ms": stage_ms.get("mlp"), "mlp_tflops": mlp_tf, "set_abstraction_fused": fused,
-                        "fps_pair_evals_per_s": B_PER_GPU * C5_S * C5_N / (stage_ms["fps"] * 1e-3) if stage_ms.get("fps") else None,
-                        "note": "HIP events around the stages of serial eager steps after the timed region"},
             "digest": [float(v) for v in digest_v],
         }
-        if not multi and not args.no_cpu_baseline:
+        if args.full:
+            fused = "group_kernel" not in stage_ms          # sa_fused.hip: gather + three layers + max in one launch (the "mlp" stage)
+            mlp_tf = B_PER_GPU * C5_MLP_FLOP_PER_CLOUD / (stage_ms["mlp"] * 1e-3) / 1e12 if stage_ms.get("mlp") else None
+            if fused:
+                roof = {"kernel": "sa_mlp3_kernel<8,32,32,64,2>", "bound": "mfma", "achieved": mlp_tf, "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s",
+                        "frac": mlp_tf / MFMA_F32_PEAK_TF if mlp_tf else None, "traffic": pmc_traffic("sa_mlp3"), "traffic_source": pmc_source("sa_mlp3"),
+                        "avg_launch_ms": stage_ms.get("mlp"), "algorithmic_flop_per_launch": B_PER_GPU * C5_MLP_FLOP_PER_CLOUD,
+                        # indices in, six gathered values per (centroid, neighbour), 64 maxima per centroid out
+                        "algorithmic_bytes_per_launch": B_PER_GPU * (C5_S * C5_K * 4 + C5_S * C5_K * 6 * 4 + 64 * C5_S * 4),
+                        "note": "the set-abstraction layer behind the ball query as one kernel (gather, 6 -> 32 -> 32 -> 64 on the fp32 MFMA, max over "
+                                "K): exact fp32 fma chains, priced against the fp32 matrix peak; the step itself is bound by furthest point "
+                                "sampling's 1024 dependent rounds (one workgroup per cloud) packed beside it, see kernels.fps_ms and config.pipeline"}
+            else:
+                grp_ms = stage_ms["group_kernel"]
+                grp_gbs = B_PER_GPU * C5_GROUP_BYTES_PER_CLOUD / (grp_ms * 1e-3) / 1e9
+                roof = {"kernel": "group_concat_kernel", "bound": "hbm", "achieved": grp_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": grp_gbs / HBM_PEAK_GBS, "traffic": pmc_traffic("group_c5"), "traffic_source": pmc_source("group_c5"),
+                        "avg_launch_ms": grp_ms, "algorithmic_bytes_per_launch": B_PER_GPU * C5_GROUP_BYTES_PER_CLOUD,
+                        "note": "microseconds of the step: the step is bound by furthest point sampling's 1024 dependent rounds "
+                                "(latency, one workgroup per cloud), see kernels.fps_ms"}
+            out.update({
+                "serial_ms_per_step": serial_ms,
+                "roofline": roof,
+                "kernels": {"fps_ms": stage_ms.get("fps"), "ball_query_ms": stage_ms.get("ball_query"), "group_ms": stage_ms.get("group_kernel"),
+                            "mlp_ms": stage_ms.get("mlp"), "mlp_tflops": mlp_tf, "set_abstraction_fused": fused,
+                            "fps_pair_evals_per_s": B_PER_GPU * C5_S * C5_N / (stage_ms["fps"] * 1e-3) if stage_ms.get("fps") else None,
+                            "note": "HIP events around the stages of serial eager steps after the timed region"},
+            })
+        if args.full and not multi and not args.no_cpu_baseline:
             out["cpu_baseline"] = c5_cpu_baseline()
     finish(out if rank == 0 else None, rank, multi, local, dist)
 
@@ -764,7 +803,7 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the untimed configs[2..4] extras (DCP-v2 forward, PCN + Chamfer, FlowNet3D sa1 / forward) of the c2 line")
     ap.add_argument("--sync-loss", action="store_true",
-                    help="N>1: make the blocking exchange the headline (default: pipelined; both are always reported)")
+                    help="N>1: make the blocking exchange the headline (default: pipelined; --full reports both)")
     ap.add_argument("--fp32-mfma", action="store_true",
                     help="run the shared-MLP GEMMs on the fp32 MFMA (157 TF peak) instead of the matrix-core split kernels")
     ap.add_argument("--arith", choices=["f16x2", "bf16x3", "fp32"], default=None,
@@ -778,10 +817,10 @@ def main():
     ap.add_argument("--fork", choices=["none", "knn", "start", "edgeconv", "conv5"], default=FORK_DEFAULT,
                     help="c2: where the step's Chamfer branch (NN search + loss tail; independent of the DGCNN chain) runs: 'knn' (default) "
                          "= on a second stream beside the kNN kernel only, joined in front of EdgeConv (two branches of the replayed "
-                         "hipGraph: both kernels are VALU / latency bound and the matrix kernels keep the chip to themselves; +1.3 %); "
+                         "hipGraph: both kernels are VALU / latency bound and the matrix kernels keep the chip to themselves; +1.3 %%); "
                          "'none' = one stream, the kernels back to back; 'start' / 'edgeconv' / 'conv5' = leaves the main stream at "
                          "the start of the step / when that stage's kernel is issued and is joined at the END of the step (measured "
-                         "2 % slower than one stream: the matrix kernels lose more than the branch gains)")
+                         "2 %% slower than one stream: the matrix kernels lose more than the branch gains)")
     ap.add_argument("--chamfer-tail", choices=["fused", "separate"], default="separate",
                     help="ChamferDistanceLoss's loss tail as its own launch behind the search (default: 0.3-0.5 %% faster inside the replayed "
                          "two-branch graph, LABLOG R6.2) or inside the search kernel's launch (l3d_chamfer_forward_loss: what the module's "
@@ -789,7 +828,17 @@ def main():
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="control-flow self test on CPU/gloo (launcher, sharding, collective, max-over-ranks, JSON): "
                          "NO kernels run and the printed line is not a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel timings and rooflines, the sustained-MFMA probe, "
+                         "the other loss-exchange mode (N>1), the untimed configs[2..4] extras and the CPU baseline "
+                         "(--no-other-configs / --no-cpu-baseline still drop those two)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed on rank 0 as DIR/<name>.npy (float32 / float64, < 64 MB): c2: "
+                         f"{FEAT_SAMPLE} DGCNN feature values at seeded positions (numpy default_rng({FEAT_SAMPLE_SEED}), sorted) "
+                         "and the Chamfer loss; c5: the set-abstraction features and the shard digest")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(relaunch_under_torchrun(args.gpus))
@@ -990,7 +1039,7 @@ def main():
         torch.cuda.synchronize()
 
     def timed(sync_loss, timer=None):
-        """K steps between two (barrier + device sync) brackets; returns (this rank's seconds, last loss)."""
+        """K steps between two (barrier + device sync) brackets; returns (this rank's seconds, last loss, last features)."""
         # steps that carry the live kernel-timing events are issued eagerly (~0.2 ms of extra host time each): at most 8
         # per run and at most one in twenty, so a 20-step run has 1 -- in the MIDDLE of its stride, where the host is several
         # queued replays ahead of the GPU and the eager step's launch work hides behind them (as the first step after the
@@ -999,38 +1048,40 @@ def main():
         stride = max(1, -(-args.steps // nsamp))
         sync()
         t0 = time.perf_counter()
-        loss = None
+        loss = feat = None
         for i in range(args.steps):
             sampled = timer is not None and i % stride == stride // 2
             if timer is not None:
                 timer.enabled = sampled
-            _, loss = step(sync_loss, eager=sampled)
+            feat, loss = step(sync_loss, eager=sampled)
         if not sync_loss:
             last = loss_pipe.flush()                      # the last step's loss, still inside the timed region
             loss = last if last is not None else loss
         sync()
-        return time.perf_counter() - t0, loss
+        return time.perf_counter() - t0, loss, feat
 
-    # Live HIP-event timing of the dominant kernel inside the timed region, on the stream it is
+    # --full: live HIP-event timing of the dominant kernel inside the timed region, on the stream it is
     # launched on (torch's current stream).  Only <= 8 evenly spaced steps carry events (they are issued eagerly,
-    # the others replay the graph).
-    timer = _fused.StageTimer(only=("edgeconv_kernel",))
+    # the others replay the graph).  A plain run replays the graph in every timed step.
+    timer = _fused.StageTimer(only=("edgeconv_kernel",)) if args.full else None
     _fused.TIMER = timer
-    elapsed, loss = timed(args.sync_loss, timer)          # THE timed region: `value` comes from this one
+    elapsed, loss, feat = timed(args.sync_loss, timer)    # THE timed region: `value` comes from this one
     _fused.TIMER = None
-    # N>1: the other exchange mode over the same K steps, reported beside the headline (the pipelined mode hides
+    if args.dump_outputs and rank == 0:                   # before anything else replays the graph (its output buffers)
+        dump_outputs(args.dump_outputs, {"dgcnn_features_sample": feature_sample(feat), "chamfer_loss": loss_array(loss)})
+    # N>1, --full: the other exchange mode over the same K steps, reported beside the headline (the pipelined mode hides
     # exactly the collective latency a scaling curve is meant to show; --sync-loss swaps which one is `value`)
     other = None
-    if multi:
+    if multi and args.full:
         for _ in range(args.warmup):
             step(not args.sync_loss)
         if args.sync_loss:
             loss_pipe.flush()
-        other, _ = timed(not args.sync_loss)
-    stage_ms = timer.mean_ms()
+        other, _, _ = timed(not args.sync_loss)
+    stage_ms = timer.mean_ms() if timer is not None else {}
     if "edgeconv_kernel" in stage_ms:                     # the live figure of the dominant kernel (events around its launch)
         stage_ms["edgeconv"] = stage_ms.pop("edgeconv_kernel")
-    # untimed diagnostics (reported under "kernels" / "roofline_knn", not part of `value`): the short
+    # --full, untimed diagnostics (reported under "kernels" / "roofline_knn", not part of `value`): the short
     # kernels are timed as 20 back-to-back launches between two events -- a per-launch event pair adds
     # ~15 us of its own to a 25-70 us kernel.
 
@@ -1051,25 +1102,26 @@ def main():
 
     import learning3d_amd.utils as U
     with torch.no_grad():
-        xt = x.permute(0, 2, 1)
-        stage_ms["knn"] = per_launch_ms(lambda: U.knn(xt, KNN))
-        stage_ms["chamfer"] = per_launch_ms(lambda: cd(a, b))
-        idx_ = U.knn(xt, KNN)
-        packed_ = net._packed.get([net.conv1, net.conv2, net.conv3, net.conv4], [net.bn1, net.bn2, net.bn3, net.bn4], x.device)
-        arith_ = _fused.gemm_arith()
-        w5_, s5_, b5_, w5s_, w5f_ = net._conv5_folded()
-        if arith_ == "f16x2":
-            v2_ = net._packed.v2_ok
-            img_ = _fused.edgeconv_forward(x, idx_, packed_, planes=True, v2=v2_, unscaled=v2_)
-            stage_ms["conv5"] = per_launch_ms(lambda: _fused.pointwise_conv_f16(img_, B_PER_GPU, NPTS, w5f_, 512, EMB, s5_, b5_, relu=True,
-                                                                                  unscaled=v2_))
-        else:
-            pooled_ = _fused.edgeconv_forward(x, idx_, packed_)
-            stage_ms["conv5"] = per_launch_ms(lambda: _fused.pointwise_conv(pooled_, w5_, s5_, b5_, relu=True, channel_last=True,
-                                                                              w_split=w5s_))
-        if "edgeconv" not in stage_ms:
-            stage_ms["edgeconv"] = per_launch_ms(lambda: _fused.edgeconv_forward(x, idx_, packed_, planes=(arith_ == "f16x2"), v2=net._packed.v2_ok,
-                                                                                   unscaled=(arith_ == "f16x2" and net._packed.v2_ok)))
+        if args.full:
+            xt = x.permute(0, 2, 1)
+            stage_ms["knn"] = per_launch_ms(lambda: U.knn(xt, KNN))
+            stage_ms["chamfer"] = per_launch_ms(lambda: cd(a, b))
+            idx_ = U.knn(xt, KNN)
+            packed_ = net._packed.get([net.conv1, net.conv2, net.conv3, net.conv4], [net.bn1, net.bn2, net.bn3, net.bn4], x.device)
+            arith_ = _fused.gemm_arith()
+            w5_, s5_, b5_, w5s_, w5f_ = net._conv5_folded()
+            if arith_ == "f16x2":
+                v2_ = net._packed.v2_ok
+                img_ = _fused.edgeconv_forward(x, idx_, packed_, planes=True, v2=v2_, unscaled=v2_)
+                stage_ms["conv5"] = per_launch_ms(lambda: _fused.pointwise_conv_f16(img_, B_PER_GPU, NPTS, w5f_, 512, EMB, s5_, b5_, relu=True,
+                                                                                      unscaled=v2_))
+            else:
+                pooled_ = _fused.edgeconv_forward(x, idx_, packed_)
+                stage_ms["conv5"] = per_launch_ms(lambda: _fused.pointwise_conv(pooled_, w5_, s5_, b5_, relu=True, channel_last=True,
+                                                                                  w_split=w5s_))
+            if "edgeconv" not in stage_ms:
+                stage_ms["edgeconv"] = per_launch_ms(lambda: _fused.edgeconv_forward(x, idx_, packed_, planes=(arith_ == "f16x2"), v2=net._packed.v2_ok,
+                                                                                       unscaled=(arith_ == "f16x2" and net._packed.v2_ok)))
         _fused.check_range(sync=True)                 # no activation left the fp16 range during the run
 
     # max over ranks (the contract), and every rank's own time for the record
@@ -1088,11 +1140,6 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         clouds_per_s = world * B_PER_GPU * args.steps / elapsed
-        ec_s = stage_ms["edgeconv"] * 1e-3
-        ec_tf = B_PER_GPU * EDGECONV_FLOP_PER_CLOUD / ec_s / 1e12
-        knn_gbs = B_PER_GPU * KNN_BYTES_PER_CLOUD / (stage_ms["knn"] * 1e-3) / 1e9
-        ch_gbs = B_PER_GPU * CHAMFER_BYTES_PER_CLOUD / (stage_ms["chamfer"] * 1e-3) / 1e9
-        c5_tf = B_PER_GPU * CONV5_FLOP_PER_CLOUD / (stage_ms["conv5"] * 1e-3) / 1e12
         arith = _fused.gemm_arith()
         dtype = {"f16x2": "f32 (shared-MLP GEMMs as f16x2: fp32 operands carried as an fp16 high part + an fp16 residual (unscaled between the EdgeConv kernel and conv5, 2^12-scaled elsewhere), "
                           "3 fp16 MFMA products per fp32 product, f32 accumulate, fp32-level error -- tests bound it by 2x the "
@@ -1131,32 +1178,40 @@ def main():
                               "path has run over RCCL with one rank and over gloo with two",
             "loss_exchange": ("blocking all_gather inside the step" if args.sync_loss else
                               "asynchronous all_gather, consumed one step later") if multi else "none (1 rank)",
-            "other_exchange_mode": None if other is None else {
-                "mode": "asynchronous all_gather, consumed one step later" if args.sync_loss else "blocking all_gather inside the step",
-                "ms_per_step": other / args.steps * 1e3, "value": world * B_PER_GPU * args.steps / other},
-            # dominant kernel by time: the fused 4-layer EdgeConv stack
-            "roofline": edgeconv_roofline(ec_tf, stage_ms["edgeconv"], arith),
-            # the metric's second half: kNN (and Chamfer) HBM rate on ALGORITHMIC bytes
-            "roofline_knn": {"kernel": "knn_mfma_kernel<8>", "bound": "hbm", "achieved": knn_gbs,
-                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": knn_gbs / HBM_PEAK_GBS,
-                             "traffic": pmc_traffic("knn_mfma") or pmc_traffic("knn"),
-                             "traffic_source": pmc_source("knn_mfma") or pmc_source("knn"),
-                             "avg_launch_ms": stage_ms["knn"],
-                             "algorithmic_bytes_per_launch": B_PER_GPU * KNN_BYTES_PER_CLOUD,
-                             "note": "VALU-bound by construction (33.5 M pair evaluations per 5.6 MB; ranking values come from the fp32 matrix cores, selection is VALU work), see DESIGN.md",
-                             "pair_evals_per_s": B_PER_GPU * NPTS * NPTS / (stage_ms["knn"] * 1e-3),
-                             "valu_frac": B_PER_GPU * NPTS * NPTS * KNN_LANEOPS_PER_PAIR /
-                             (stage_ms["knn"] * 1e-3) / VALU_PEAK_LANEOPS,
-                             **knn_executed(stage_ms["knn"])},
-            "kernels": {"knn_ms": stage_ms["knn"], "edgeconv_ms": stage_ms["edgeconv"], "conv5_ms": stage_ms["conv5"],
-                        "chamfer_ms": stage_ms["chamfer"], "conv5_tflops": c5_tf, "chamfer_alg_gbs": ch_gbs,
-                        "chamfer_valu_frac": 2 * B_PER_GPU * NPTS * NPTS * CHAMFER_LANEOPS_PER_PAIR /
-                        (stage_ms["chamfer"] * 1e-3) / VALU_PEAK_LANEOPS,
-                        "knn_chamfer_alg_gbs": B_PER_GPU * (KNN_BYTES_PER_CLOUD + CHAMFER_BYTES_PER_CLOUD) /
-                        ((stage_ms["knn"] + stage_ms["chamfer"]) * 1e-3) / 1e9},
             "loss": float(loss),
         }
-        if not multi and arith in SPLIT_PRODUCTS:
+        if args.full:
+            ec_s = stage_ms["edgeconv"] * 1e-3
+            ec_tf = B_PER_GPU * EDGECONV_FLOP_PER_CLOUD / ec_s / 1e12
+            knn_gbs = B_PER_GPU * KNN_BYTES_PER_CLOUD / (stage_ms["knn"] * 1e-3) / 1e9
+            ch_gbs = B_PER_GPU * CHAMFER_BYTES_PER_CLOUD / (stage_ms["chamfer"] * 1e-3) / 1e9
+            c5_tf = B_PER_GPU * CONV5_FLOP_PER_CLOUD / (stage_ms["conv5"] * 1e-3) / 1e12
+            out.update({
+                "other_exchange_mode": None if other is None else {
+                    "mode": "asynchronous all_gather, consumed one step later" if args.sync_loss else "blocking all_gather inside the step",
+                    "ms_per_step": other / args.steps * 1e3, "value": world * B_PER_GPU * args.steps / other},
+                # dominant kernel by time: the fused 4-layer EdgeConv stack
+                "roofline": edgeconv_roofline(ec_tf, stage_ms["edgeconv"], arith),
+                # the metric's second half: kNN (and Chamfer) HBM rate on ALGORITHMIC bytes
+                "roofline_knn": {"kernel": "knn_mfma_kernel<8>", "bound": "hbm", "achieved": knn_gbs,
+                                 "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": knn_gbs / HBM_PEAK_GBS,
+                                 "traffic": pmc_traffic("knn_mfma") or pmc_traffic("knn"),
+                                 "traffic_source": pmc_source("knn_mfma") or pmc_source("knn"),
+                                 "avg_launch_ms": stage_ms["knn"],
+                                 "algorithmic_bytes_per_launch": B_PER_GPU * KNN_BYTES_PER_CLOUD,
+                                 "note": "VALU-bound by construction (33.5 M pair evaluations per 5.6 MB; ranking values come from the fp32 matrix cores, selection is VALU work), see DESIGN.md",
+                                 "pair_evals_per_s": B_PER_GPU * NPTS * NPTS / (stage_ms["knn"] * 1e-3),
+                                 "valu_frac": B_PER_GPU * NPTS * NPTS * KNN_LANEOPS_PER_PAIR /
+                                 (stage_ms["knn"] * 1e-3) / VALU_PEAK_LANEOPS,
+                                 **knn_executed(stage_ms["knn"])},
+                "kernels": {"knn_ms": stage_ms["knn"], "edgeconv_ms": stage_ms["edgeconv"], "conv5_ms": stage_ms["conv5"],
+                            "chamfer_ms": stage_ms["chamfer"], "conv5_tflops": c5_tf, "chamfer_alg_gbs": ch_gbs,
+                            "chamfer_valu_frac": 2 * B_PER_GPU * NPTS * NPTS * CHAMFER_LANEOPS_PER_PAIR /
+                            (stage_ms["chamfer"] * 1e-3) / VALU_PEAK_LANEOPS,
+                            "knn_chamfer_alg_gbs": B_PER_GPU * (KNN_BYTES_PER_CLOUD + CHAMFER_BYTES_PER_CLOUD) /
+                            ((stage_ms["knn"] + stage_ms["chamfer"]) * 1e-3) / 1e9},
+            })
+        if args.full and not multi and arith in SPLIT_PRODUCTS:
             try:        # the roofline's denominator, re-measured: the matrix rate this box sustains under an all-MFMA load
                 sus = mfma_sustained(dev)
                 prods = SPLIT_PRODUCTS[arith]
@@ -1169,9 +1224,9 @@ def main():
                             "assumes a 2.4 GHz shader clock this load does not hold"}
             except Exception as exc:
                 out["roofline"]["sustained"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if not multi and not args.no_other_configs:
+        if args.full and not multi and not args.no_other_configs:
             out["other_configs"] = other_configs(dev)
-        if not multi and not args.no_cpu_baseline:
+        if args.full and not multi and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
             out["cpu_baseline"]["loss_matches_gpu_step"] = abs(out["cpu_baseline"]["loss"] - out["loss"]) < 1e-6
     finish(out if rank == 0 else None, rank, multi, local, dist)

@@ -6,15 +6,16 @@
 set -u
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R; mkdir -p gpurun_out; export PYTHONUNBUFFERED=1
+B=${BENCH_OUT_DIR:-bench_out}; mkdir -p $B      # the bench tasks' JSON lines and logs (set BENCH_OUT_DIR to the folder the caller collects)
 for task in "$@"; do
   name=${task%%:*}; arg=${task#*:}; [ "$arg" = "$task" ] && arg=""
   echo "=== $task"
   case $name in
     tests)  if [ -n "$arg" ]; then timeout 2400 python -m pytest tests -m gpu -x -q -k "$arg" 2>&1 | tail -15;
             else timeout 3000 python -m pytest tests -m gpu -x -q 2>&1 | tail -15; fi ;;
-    bench)  timeout 900 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err; tail -c 1500 gpurun_out/bench.json | head -c 1500; echo; tail -3 gpurun_out/bench.err ;;
-    bench_driver) for i in 1 2 3; do timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline > gpurun_out/bench_driver_$i.json 2>> gpurun_out/bench.err;
-              python - gpurun_out/bench_driver_$i.json <<'PY'
+    bench)  timeout 900 python bench.py --full > $B/bench.json 2> $B/bench.err; tail -c 1500 $B/bench.json | head -c 1500; echo; tail -3 $B/bench.err ;;
+    bench_driver) for i in 1 2 3; do timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-other-configs --no-cpu-baseline > $B/bench_driver_$i.json 2>> $B/bench.err;
+              python - $B/bench_driver_$i.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d["roofline"]

@@ -75,8 +75,8 @@ def test_bench_multi_rank_path_over_rccl_one_rank(workload):
     import json
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=_free_port(), WORLD_SIZE="1", RANK="0",
                LOCAL_RANK="0", L3D_INIT_SINGLE_RANK="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline",
-           "--workload", workload]
+    plain = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"]
+    cmd = plain + ["--full", "--workload", workload]                 # --full: both exchange modes are timed
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = p.stdout.decode().strip().splitlines()
@@ -88,7 +88,7 @@ def test_bench_multi_rank_path_over_rccl_one_rank(workload):
         assert d["loss_exchange"].startswith("asynchronous all_gather") and d["other_exchange_mode"]["mode"].startswith("blocking")
         assert d["other_exchange_mode"]["ms_per_step"] > 0
         # the same loss as a plain one-process run of the same seeded step
-        q = subprocess.run(cmd[:-2], env={k: v for k, v in os.environ.items()}, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+        q = subprocess.run(plain, env={k: v for k, v in os.environ.items()}, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
         assert q.returncode == 0, q.stderr.decode()[-3000:]
         e = json.loads(q.stdout.decode().strip().splitlines()[-1])
         assert e["dist_backend"] is None and abs(e["loss"] - d["loss"]) <= 1e-6 * abs(e["loss"]), (e["loss"], d["loss"])
