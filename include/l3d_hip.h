@@ -65,7 +65,9 @@ int l3d_knn_graph(const float *xyz, int B, int N, int k, int64_t *idx, l3d_strea
  *                    src[b][c][e / div] * (weight ? weight[b][e] : 1)
  * src fp32 [B][C][E/div]; idx int32 [B][E] with values in [0,T); dst fp32 [B][C][T] (fully written).
  * grouping: E = npoint*nsample, div 1;  gather: E = npoint, div 1;  three_interpolate: E = n*3, div 3, weight [B,n,3].
- * workspace: >= l3d_scatter_add_det_workspace_bytes(B,T,E) bytes.  Same inputs -> same bits, every run. */
+ * workspace: >= l3d_scatter_add_det_workspace_bytes(B,T,E) bytes.  Same inputs -> same bits, every run.
+ * T * R >= 2^22 (R = 1, 2, 4, 8 placement ranges for E <= 1024, 3072, 7168, more), B*T or B*E >= 2^31, B or C > 65535
+ *   -> L3D_ERR_UNSUPPORTED (the Python wrapper splits the targets into windows). */
 size_t l3d_scatter_add_det_workspace_bytes(int B, int T, int E);
 int l3d_scatter_add_det(const float *src, const int32_t *idx, const float *weight, int B, int C, int T, int E, int div,
                         void *workspace, float *dst, l3d_stream_t stream);
@@ -80,12 +82,13 @@ int l3d_scatter_add_det(const float *src, const int32_t *idx, const float *weigh
 int l3d_edge_gather_max(const float *pq, const int64_t *idx, int B, int Cout, int N, int k, int act, float *out,
                         long out_bstride, l3d_stream_t stream);
 
-/* knn() of utils/model_common_utils.py:3-9 for FEATURE-space graphs, x [B,C,N] with C % 32 == 0 (PRNet's
+/* knn() of utils/model_common_utils.py:3-9 for FEATURE-space graphs, x [B,C,N], any C (zero-padded to a multiple of 64; PRNet's
  * dynamic DGCNN graphs, models/prnet.py:76-97; C = 3 takes l3d_knn_graph): pd = -xx_j + 2 x_i.x_j - xx_i
  * with the inner product on the matrix cores (bf16x3, fp32-level error) and top-k as the GEMM epilogue, no
  * [B,N,N] tensor.  idx int64 [B,N,k], best first, exact ties -> lower index.  workspace: >=
  * l3d_knn_feature_workspace_bytes(B,C,N) bytes, 16-byte aligned (holds the split copy of x).
- * k > 20 or C % 32 != 0 -> L3D_ERR_UNSUPPORTED; k > N -> L3D_ERR_INVALID_ARG. */
+ * k > 64, N > 16384 (N rounded up to 128 past FK_MAXNP), B > 65535 or a misaligned workspace -> L3D_ERR_UNSUPPORTED;
+ * k > N -> L3D_ERR_INVALID_ARG. */
 size_t l3d_knn_feature_workspace_bytes(int B, int C, int N);
 int l3d_knn_feature(const float *x, int B, int C, int N, int k, void *workspace, int64_t *idx, l3d_stream_t stream);
 
@@ -163,7 +166,8 @@ int l3d_gather_points_grad(int b, int c, int n, int npoints, const float *grad_o
                            const int32_t *idx, float *grad_points, l3d_stream_t stream);
 /* furthest_point_sampling_wrapper(b,n,m,points,temp,idx)   K12 sampling_gpu.cu:93-209
  *   points [B,n,3]; temp [B,n] scratch (callee initialises it to 1e10); idx [B,m] int32;
- *   starts at index 0. */
+ *   starts at index 0.  n <= 16384: temp may be NULL (the cloud stays in registers; temp, when given, receives the final
+ *   distances); n > 16384: temp is required (NULL -> L3D_ERR_INVALID_ARG); n >= 2^25 -> L3D_ERR_UNSUPPORTED. */
 int l3d_furthest_point_sampling(int b, int n, int m, const float *points, float *temp,
                                 int32_t *idx, l3d_stream_t stream);
 /* knn_wrapper(b,n,m,k,unknown,known,dist2,idx)   K13 interpolate_gpu.cu:9-57
@@ -207,7 +211,8 @@ int l3d_query_ball_point(float radius, int nsample, const float *xyz, const floa
 int l3d_index_points(const float *points, const int64_t *idx, int B, int N, int C, int S,
                      float *out, l3d_stream_t stream);
 /* farthest_point_sample(xyz, npoint) :58-82: start[b] gives the first centroid (the reference
- *   draws it with torch.randint; start == NULL means index 0); temp [B,N] scratch. */
+ *   draws it with torch.randint; start == NULL means index 0); temp [B,N] scratch, with the limits of
+ *   l3d_furthest_point_sampling (required for N > 16384). */
 int l3d_farthest_point_sample(const float *xyz, int B, int N, int npoint, const int64_t *start,
                               float *temp, int64_t *centroids, l3d_stream_t stream);
 /* knn_point(k,pos1,pos2) :84-100: pos1 [B,N,3] searched, pos2 [B,M,3] queries ->

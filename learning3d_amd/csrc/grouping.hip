@@ -885,6 +885,69 @@ __global__ __launch_bounds__(PPT >= 8 ? 512 : 1024) void fps_kernel(int n, int m
     }
 }
 
+// Clouds past the register-resident kernel's 512 x 32 points: the reference's own scheme (sampling_gpu.cu:93-209) -- 1024 threads,
+// thread tid owns k = tid, tid + 1024, ..., and the running minimum distances live in the caller's temp [B][n] -- with
+// fps_kernel's arg-max and tie rule.  Each thread scans its points in ascending k with a strict '>', so its candidate is its lowest
+// index among equal maxima; across threads tkey() decides (OUT64: lowest index; pointnet2: bit-reversed thread id at T = 1024 --
+// opt_n_threads(n) for every n >= 1024 -- then index).  A thread reads back only the temp slots it wrote: no barrier on temp.
+template <bool OUT64>
+__global__ __launch_bounds__(1024) void fps_big_kernel(int n, int m, const float *__restrict__ xyz, const int64_t *__restrict__ start,
+                                                       float *__restrict__ temp, void *__restrict__ out)
+{
+    __shared__ int wv[2][16];
+    __shared__ int wi[2][16];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const float *p = xyz + (size_t)b * n * 3;
+    float *tb = temp + (size_t)b * n;
+    for (int k = tid; k < n; k += 1024) tb[k] = 1e10f;
+    if (tid < 32) { wv[tid >> 4][tid & 15] = (int)0x80000000; wi[tid >> 4][tid & 15] = 0x7fffffff; }
+    int old = (OUT64 && start) ? (int)start[b] : 0;
+    if (tid == 0) {
+        if (OUT64) ((int64_t *)out)[(size_t)b * m] = old; else ((int32_t *)out)[(size_t)b * m] = old;
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    constexpr int lt = 10;
+    auto brev = [&](int x) { return (int)(__builtin_bitreverse32((unsigned)x) >> (32 - lt)); };
+    auto tkey = [&](int k) { return OUT64 ? k : ((brev(k & ((1 << lt) - 1)) << 15) | (k >> lt)); };
+    auto tinv = [&](int q) { return OUT64 ? q : (((q & 0x7fff) << lt) | brev(q >> 15)); };
+    for (int j = 1; j < m; j++) {
+        const float x1 = p[(size_t)old * 3], y1 = p[(size_t)old * 3 + 1], z1 = p[(size_t)old * 3 + 2];
+        int best = (int)0x80000000;
+        int besti = 0;
+        for (int k = tid; k < n; k += 1024) {
+            const float dx = p[(size_t)k * 3] - x1, dy = p[(size_t)k * 3 + 1] - y1, dz = p[(size_t)k * 3 + 2] - z1;
+            const float d = (dx * dx + dy * dy) + dz * dz;
+            const float d2 = fminf(d, tb[k]);
+            tb[k] = d2;
+            const int key = __builtin_bit_cast(int, d2);
+            const bool gt = key > best;
+            best = gt ? key : best;
+            besti = gt ? k : besti;
+        }
+        const int wmax = wave_max_i(best);
+        const unsigned long long hit = __ballot(best == wmax);
+        int widx;
+        if (__builtin_popcountll(hit) == 1)
+            widx = __builtin_amdgcn_readlane(besti, __builtin_ctzll(hit));
+        else
+            widx = tinv(wave_min_i(best == wmax ? tkey(besti) : 0x7fffffff));
+        const int buf = j & 1;
+        if (lane == 0) { wv[buf][wave] = wmax; wi[buf][wave] = widx; }
+        __syncthreads();
+        const int ev = wv[buf][lane & 15], ei = wi[buf][lane & 15];
+        const int bmax = row16_max_i(ev);
+        const unsigned hit16 = (unsigned)(__ballot(ev == bmax) & 0xffffull);
+        if (__builtin_popcount(hit16) == 1)
+            old = __builtin_amdgcn_readlane(ei, __builtin_ctz(hit16));
+        else
+            old = __builtin_amdgcn_readfirstlane(tinv(row16_min_i(ev == bmax ? tkey(ei) : 0x7fffffff)));
+        if (tid == 0) {
+            if (OUT64) ((int64_t *)out)[(size_t)b * m + j] = old; else ((int32_t *)out)[(size_t)b * m + j] = old;
+        }
+    }
+}
+
 template <bool OUT64>
 static int launch_fps(int b, int n, int m, const float *xyz, const int64_t *start, float *temp,
                       void *out, hipStream_t st)
@@ -911,7 +974,11 @@ static int launch_fps(int b, int n, int m, const float *xyz, const int64_t *star
     L3D_FPS_CASE(16)
     L3D_FPS_CASE(32)
 #undef L3D_FPS_CASE
-    return L3D_ERR_UNSUPPORTED;       // > 32768 points per cloud
+    // > 16384 points per cloud: the minimum distances in temp (required here), tkey()'s 15 index bits bound the cloud
+    if (!temp) return L3D_ERR_INVALID_ARG;
+    if (n >= (1 << 25)) return L3D_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((fps_big_kernel<OUT64>), dim3(b), dim3(1024), 0, st, n, m, xyz, start, temp, out);
+    return l3d_check_launch();
 }
 
 extern "C" int l3d_furthest_point_sampling(int b, int n, int m, const float *points, float *temp,

@@ -229,7 +229,8 @@ __global__ __launch_bounds__(1024) void sd_sum_lds_kernel(const float *__restric
 }
 
 static size_t sd_align(size_t x) { return (x + 255) & ~(size_t)255; }
-// ranges per cloud: up to 8 placement workgroups per cloud, each a whole number of 1024-entry chunks
+// ranges per cloud: up to 8 placement workgroups per cloud, each a whole number of 1024-entry chunks.  Restated in Python with the
+// entry point's size guards (utils/pointnet2_utils.py: _sd_ranges / _sd_fits, which split the refused shapes into windows): change both
 static int sd_ranges(int E) { const int chunks = l3d_divup(E, 1024); return chunks >= 8 ? 8 : (chunks >= 4 ? 4 : (chunks >= 2 ? 2 : 1)); }
 
 extern "C" size_t l3d_scatter_add_det_workspace_bytes(int B, int T, int E)
@@ -250,7 +251,8 @@ extern "C" int l3d_scatter_add_det(const float *src, const int32_t *idx, const f
     unsigned char *w = (unsigned char *)(((size_t)workspace + 255) & ~(size_t)255);
     const int R = sd_ranges(E), rlen = l3d_divup(l3d_divup(E, R), 1024) * 1024;
     const long slots = targets * R;
-    if ((long)T * R > (1L << 22)) return L3D_ERR_UNSUPPORTED;
+    // a placement word is (target << 10 | lane) with 0xFFFFFFFF as padding: T = 2^22 would put target 2^22 - 1, lane 1023 on it
+    if ((long)T * R >= (1L << 22)) return L3D_ERR_UNSUPPORTED;
     const size_t seg = sd_align((size_t)total * 4), tseg = sd_align((size_t)(slots + 1) * 4);
     uint32_t *order = (uint32_t *)w;
     unsigned *counts = (unsigned *)(w + seg);

@@ -51,6 +51,7 @@ def bmm(a, b, alpha=1.0, out=None, relu=False, bias=None, bias_axis="n", accumul
     if K != K2:
         raise RuntimeError(f"bmm: inner dimensions {K} and {K2} differ")
     a4, b4 = a4.expand(nb1, nb2, M, K), b4.expand(nb1, nb2, K, N)
+    given = out is not None
     if out is None:
         out = torch.empty(tuple(torch.broadcast_shapes(a.shape[:-2], b.shape[:-2])) + (M, N), dtype=torch.float32, device=a.device)
     if min(M, N, K, nb1, nb2) == 0:
@@ -67,6 +68,9 @@ def bmm(a, b, alpha=1.0, out=None, relu=False, bias=None, bias_axis="n", accumul
     with on_device_of(a):
         check(lib().l3d_bmm_f32(ptr(a4), _st(a4), ptr(b4), _st(b4), ptr(o4), _st(o4), nb1, nb2, M, N, K, float(alpha), flags, ptr(bias),
                                 int(parts), ptr(ws), stream_ptr()), "l3d_bmm_f32")
+    if given:
+        # a write through the raw pointer: bump the version autograd and _row_operand's image cache key on
+        torch.autograd.graph.increment_version(out)
     return out
 
 
@@ -239,7 +243,7 @@ class _LinearRows(torch.autograd.Function):
 
 def colsum(g):
     """sum over the rows of g [R, C] (a bias gradient): l3d_colsum_rows, fixed summation order"""
-    if g.stride(1) != 1:
+    if g.stride(1) != 1 or g.stride(0) < g.shape[1]:        # the kernel reads rows of row_stride >= cols (not expanded ones)
         g = g.contiguous()
     R, Cn = g.shape
     out = torch.empty(Cn, dtype=torch.float32, device=g.device)
@@ -318,12 +322,8 @@ class _IndexPoints(torch.autograd.Function):
         B, S = ix.shape
         Cc = g.shape[-1]
         src = f32c(g.reshape(B, S, Cc).transpose(1, 2))                                      # [B,C,S]
-        i32 = ix.to(torch.int32)
-        dst = torch.empty((B, Cc, ctx.n), dtype=torch.float32, device=g.device)
-        with on_device_of(src):
-            ws = torch.empty(lib().l3d_scatter_add_det_workspace_bytes(B, ctx.n, S), dtype=torch.uint8, device=g.device)
-            check(lib().l3d_scatter_add_det(ptr(src), ptr(i32), None, B, Cc, ctx.n, S, 1, ptr(ws), ptr(dst), stream_ptr()),
-                  "l3d_scatter_add_det")
+        from ..utils.pointnet2_utils import _scatter_add_det
+        dst = _scatter_add_det(src, ix.to(torch.int32), None, ctx.n, 1)
         return dst.transpose(1, 2), None
 
 

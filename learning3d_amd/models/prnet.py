@@ -22,6 +22,8 @@ from .._lib import check, lib, ptr, stream_ptr
 from ..utils.model_common_utils import get_graph_feature, knn
 from . import _fused
 
+EDGE_GATHER_MAX_N = 32768       # l3d_edge_gather_max stages a channel row of N floats in LDS (<= 128 KiB); longer clouds take the
+                                # per-layer route below (graph feature + conv / BN / max on the HIP layers)
 NEG_SLOPE = 0.2                                                           # prnet.py:79-95
 ACT_LRELU = struct.unpack("<i", struct.pack("<f", NEG_SLOPE))[0]          # activation code: the slope's fp32 bits
 
@@ -67,7 +69,7 @@ class DGCNN(torch.nn.Module):
 
     def _forward(self, x):
         batch_size, num_dims, num_points = x.size()
-        if _fused.can_fuse(self, x) and x.is_cuda:
+        if _fused.can_fuse(self, x) and x.is_cuda and num_points <= EDGE_GATHER_MAX_N:
             B, N = batch_size, num_points
             cat = torch.empty((B, 512, N), dtype=torch.float32, device=x.device)
             h, lo = x.float().contiguous(), 0

@@ -17,6 +17,27 @@ def _as_bn3(x_bcn):
     return f32c(xt)
 
 
+_FEATKNN_MAX_N = 16384      # featknn.hip FK_MAXNP: l3d_knn_feature's longest cloud
+
+
+def _knn_feature_rows(xf, k, elems=1 << 25):
+    """the reference's knn (utils/model_common_utils.py:4-8) on x [B,C,N] fp32 for blocks of query rows: at most `elems` distances
+    at a time instead of the [B,N,N] matrix"""
+    B, _, N = xf.shape
+    xx = torch.sum(xf ** 2, dim=1, keepdim=True)                 # [B,1,N]
+    xt = xf.transpose(2, 1)
+    q = max(1, elems // (B * N))
+    if q >= N:
+        inner = -2 * torch.matmul(xt, xf)
+        return (-xx - inner - xx.transpose(2, 1)).topk(k=k, dim=-1)[1]
+    idx = torch.empty((B, N, k), dtype=torch.int64, device=xf.device)
+    for q0 in range(0, N, q):
+        inner = -2 * torch.matmul(xt[:, q0:q0 + q], xf)
+        pd = -xx - inner - xx.transpose(2, 1)[:, q0:q0 + q]
+        idx[:, q0:q0 + q] = pd.topk(k=k, dim=-1)[1]
+    return idx
+
+
 def knn(x, k, add_one_to_k=False):
     """reference: utils/model_common_utils.py:3-9.   x [B,3,N] -> idx int64 [B,N,k].
 
@@ -35,16 +56,14 @@ def knn(x, k, add_one_to_k=False):
         # feature-space graphs (PRNet's DGCNN, models/prnet.py:76-97; C = 64..256): the distance is a real
         # GEMM -> matrix cores (bf16x3) with the top-k as its epilogue, no [B,N,N] tensor
         xf = f32c(x)
-        if k <= 64:                                              # any C (zero-padded to a multiple of 32 in the split pass)
+        if k <= 64 and N <= _FEATKNN_MAX_N:                     # any C (zero-padded to a multiple of 64 in the split pass)
             ws = torch.empty(lib().l3d_knn_feature_workspace_bytes(B, Cc, N), dtype=torch.uint8, device=x.device)
             idx = torch.empty((B, N, k), dtype=torch.int64, device=x.device)
             check(lib().l3d_knn_feature(ptr(xf), B, Cc, N, k, ptr(ws), ptr(idx), stream_ptr()), "l3d_knn_feature")
             return idx
-        # k > 64 in feature space: no caller in the reference asks for it; the op sequence itself (:4-8) on the device
-        inner = -2 * torch.matmul(xf.transpose(2, 1), xf)
-        xx = torch.sum(xf ** 2, dim=1, keepdim=True)
-        pairwise_distance = -xx - inner - xx.transpose(2, 1)
-        return pairwise_distance.topk(k=k, dim=-1)[1]
+        # k > 64 (no caller in the reference asks for it) or a cloud past the kernel's key range: the op sequence itself (:4-8)
+        # on the device, a block of queries at a time
+        return _knn_feature_rows(xf, k)
     xyz = _as_bn3(x)
     idx = torch.empty((B, N, k), dtype=torch.int64, device=x.device)
     check(lib().l3d_knn_graph(ptr(xyz), B, N, k, ptr(idx), stream_ptr()), "l3d_knn_graph")
@@ -110,7 +129,9 @@ def farthest_point_sample(xyz, npoint, start_with_first_point=False):
     else:
         start = None
     cent = torch.empty((B, npoint), dtype=torch.int64, device=xyz.device)
-    check(lib().l3d_farthest_point_sample(ptr(x), B, N, npoint, ptr(start), None, ptr(cent), stream_ptr()),
+    from .pointnet2_utils import FPS_REGISTER_N
+    temp = torch.empty((B, N), dtype=torch.float32, device=xyz.device) if N > FPS_REGISTER_N else None   # scratch past it
+    check(lib().l3d_farthest_point_sample(ptr(x), B, N, npoint, ptr(start), ptr(temp), ptr(cent), stream_ptr()),
           "l3d_farthest_point_sample")
     return cent
 
@@ -180,11 +201,8 @@ class _GraphFeature(torch.autograd.Function):
         # (l3d_scatter_add_det, scatter_det.hip) -- deterministic, unlike index_add's fp32 atomics
         src = g[..., :Cc].permute(0, 3, 1, 2).reshape(B, Cc, N * k).contiguous()
         idx32 = idx.to(torch.int32).reshape(B, N * k).contiguous()
-        dst = torch.empty((B, Cc, N), dtype=torch.float32, device=g.device)
-        ws = torch.empty(lib().l3d_scatter_add_det_workspace_bytes(B, N, N * k), dtype=torch.uint8, device=g.device)
-        check(lib().l3d_scatter_add_det(ptr(src), ptr(idx32), None, B, Cc, N, N * k, 1, ptr(ws), ptr(dst), stream_ptr()),
-              "l3d_scatter_add_det")
-        return dst + centre, None
+        from .pointnet2_utils import _scatter_add_det
+        return _scatter_add_det(src, idx32, None, N, 1) + centre, None
 
 
 def get_graph_feature(x, k=20, device=None):

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from .._lib import check, f32c, lib, ptr, require_gpu, stream_ptr
+from .._lib import check, f32c, lib, on_device_of, ptr, require_gpu, stream_ptr
 
 
 # Backward of the gather-type ops: True = every target owns its sum and adds its contributions in ascending
@@ -22,15 +22,54 @@ from .._lib import check, f32c, lib, ptr, require_gpu, stream_ptr
 DETERMINISTIC_BACKWARD = True
 
 
-def _scatter_add_det(src, idx, weight, T, div):
-    """dst[b,c,t] = sum_{e: idx[b,e]==t, ascending e} src[b,c,e//div] * weight[b,e];  src [B,C,E/div], idx int32 [B,E]"""
+def _sd_ranges(E):
+    """scatter_det.hip's sd_ranges: placement workgroups per cloud (kept in step with it: tests/test_scatter_key_model.py checks
+    the library's refusal one target past every class's limit)"""
+    chunks = -(-E // 1024)
+    return 8 if chunks >= 8 else 4 if chunks >= 4 else 2 if chunks >= 2 else 1
+
+
+def _sd_fits(B, T, E):
+    """the shapes l3d_scatter_add_det takes (its guards): T * ranges < 2^22 -- a placement word is (target << 10 | lane), and
+    0xFFFFFFFF is its padding -- and fewer than 2^31 entries / targets over the batch"""
+    return T * _sd_ranges(E) < (1 << 22) and B * T < (1 << 31) and B * E < (1 << 31)
+
+
+def _scatter_add_det_call(src, idx, weight, T, div, dst):
     B, Cc = src.shape[0], src.shape[1]
     E = idx.numel() // B
-    dst = torch.empty((B, Cc, T), dtype=torch.float32, device=src.device)
     ws = torch.empty(lib().l3d_scatter_add_det_workspace_bytes(B, T, E), dtype=torch.uint8, device=src.device)
     check(lib().l3d_scatter_add_det(ptr(src), ptr(idx), ptr(weight), B, Cc, T, E, div, ptr(ws), ptr(dst), stream_ptr()),
           "l3d_scatter_add_det")
+
+
+def _scatter_add_det(src, idx, weight, T, div):
+    """dst[b,c,t] = sum_{e: idx[b,e]==t, ascending e} src[b,c,e//div] * weight[b,e];  src [B,C,E/div], idx int32 [B,E].
+    The backward of every gather-type op (grouping, gather, three_interpolate, index_points, get_graph_feature) goes through here.
+    More targets than the kernel takes: windows of W targets, each one kernel call with one spare target W that every entry
+    outside the window is sent to (its row is dropped).  A window's entries keep their ascending order, so every sum is the
+    same as in one call -- bit for bit.  The cost of that: every window places and sums all E entries again, and its spare
+    target's segment holds the entries of every other window, summed serially -- fine for the few windows past 2^22 / ranges
+    targets, not a fast path (no benchmark shape reaches it)."""
+    B, Cc = src.shape[0], src.shape[1]
+    E = idx.numel() // B
+    dst = torch.empty((B, Cc, T), dtype=torch.float32, device=src.device)
+    with on_device_of(src):
+        if _sd_fits(B, T, E):
+            _scatter_add_det_call(src, idx, weight, T, div, dst)
+            return dst
+        W = min((1 << 22) // _sd_ranges(E) - 2, (1 << 31) // B - 2)
+        ix = idx.reshape(B, E).clamp(0, T - 1)                     # the kernel clamps out-of-range indices the same way
+        part = torch.empty((B, Cc, W + 1), dtype=torch.float32, device=src.device)
+        for t0 in range(0, T, W):
+            w = min(W, T - t0)
+            iw = torch.where((ix >= t0) & (ix < t0 + w), ix - t0, W).to(torch.int32)
+            _scatter_add_det_call(src, iw, weight, W + 1, div, part)
+            dst[:, :, t0:t0 + w] = part[:, :, :w]
     return dst
+
+
+FPS_REGISTER_N = 16384      # grouping.hip launch_fps: up to 512 threads x 32 points keep the cloud in registers, no scratch
 
 
 class FurthestPointSampling(Function):
@@ -42,7 +81,9 @@ class FurthestPointSampling(Function):
         require_gpu(xyz)
         B, N, _ = xyz.size()
         output = torch.empty((B, npoint), dtype=torch.int32, device=xyz.device)
-        check(lib().l3d_furthest_point_sampling(B, N, npoint, ptr(xyz), None, ptr(output), stream_ptr()),
+        # past FPS_REGISTER_N points the kernel keeps the running distances in temp, like the reference (:25-28)
+        temp = torch.empty((B, N), dtype=torch.float32, device=xyz.device) if N > FPS_REGISTER_N else None
+        check(lib().l3d_furthest_point_sampling(B, N, npoint, ptr(xyz), ptr(temp), ptr(output), stream_ptr()),
               "l3d_furthest_point_sampling")
         ctx.mark_non_differentiable(output)
         return output

@@ -67,7 +67,7 @@ def clouds(B, N, seed, clip=2.0):
 
 
 # ----------------------------------------------------------------------------------------- K12 FPS
-@pytest.mark.parametrize("B,N,S", [(3, 2000, 256), (2, 8192, 1024), (4, 100, 100), (2, 513, 17)])
+@pytest.mark.parametrize("B,N,S", [(3, 2000, 256), (2, 8192, 1024), (4, 100, 100), (2, 513, 17), (2, 16385, 64), (2, 65536, 64)])
 def test_fps_equals_reference_kernel(PN, B, N, S):
     from learning3d_amd.utils import pointnet2_utils as P
     xyz = dev(clouds(B, N, 1))
@@ -332,7 +332,8 @@ def test_config5_fps_and_ball_query_all_32_clouds_equal_reference_kernels(PN):
     assert torch.equal(gq, wq)
 
 
-@pytest.mark.parametrize("N,S", [(300, 64), (1100, 128), (2500, 200), (8192, 256), (16384, 64)])
+@pytest.mark.parametrize("N,S", [(300, 64), (1100, 128), (2500, 200), (8192, 256), (16384, 64), (16385, 64), (24577, 64),
+                                 (32768, 64), (32769, 64), (65536, 64), (262144, 64)])
 def test_fps_ties_resolve_like_the_reference_kernel(PN, N, S):
     """Clouds clipped hard (N(0,1) to [-1,1]: hundreds of duplicated corner / edge points) tie in almost every early round of
     furthest point sampling.  The reference kernel resolves a tie by its block tree (bit-reversed thread id, then index), not by

@@ -81,6 +81,15 @@ def test_argument_validation_without_gpu():
     assert l.l3d_layernorm_ref_backward(p, p, p, 1e-6, 4, 66, p, p, p, p, None) == -2                              # C % 4
     assert l.l3d_layernorm_backward_workspace_floats(8192, 512) == 256 * 2 * 512
     assert l.l3d_layernorm_backward_workspace_floats(6, 64) == 2 * 2 * 64
+    # size limits, refused before any launch (the Python wrappers route these shapes elsewhere and must not raise)
+    assert l.l3d_scatter_add_det(p, p, None, 1, 2, 1 << 22, 1024, 1, p, p, None) == -2          # (target << 10 | lane) would reach 0xFFFFFFFF
+    assert l.l3d_scatter_add_det(p, p, None, 1, 2, 1 << 21, 2048, 1, p, p, None) == -2          # two placement ranges: T * 2 >= 2^22
+    assert l.l3d_scatter_add_det(p, p, None, 1, 2, 524288, 8192, 1, p, p, None) == -2           # eight ranges: T * 8 >= 2^22
+    assert l.l3d_furthest_point_sampling(1, 16385, 64, p, None, p, None) == -1                  # past 512 x 32 points: temp required
+    assert l.l3d_farthest_point_sample(p, 1, 16385, 64, None, None, p, None) == -1
+    assert l.l3d_furthest_point_sampling(1, 1 << 25, 64, p, p, p, None) == -2                   # tie key: 15 bits of k >> 10
+    assert l.l3d_knn_feature(p, 1, 64, 16385, 20, p, p, None) == -2                             # FK_MAXNP = 16384
+    assert l.l3d_edge_gather_max(p, p, 1, 64, 32769, 20, 0, p, 64 * 32769, None) == -2          # a channel row of N floats in LDS
 
 
 def test_product_path_fails_loudly_on_cpu_tensors():
