@@ -19,7 +19,7 @@ int main()
     printf("---- %s\n", dbg ? "no candidate reaches the threshold (pass 1 = tiles + masks only, empty lists)" : "normal");
     for (int it = 0; it < 3; it++) l3d_launch_knn_mfma(x, B, N, k + 256 * dbg, (int64_t *)out, 0);
     hipDeviceSynchronize();
-    const int nw = B * (N / 32) * 4;
+    const int nw = B * (N / 64) * 8;                 // 64 queries, 8 waves per workgroup
     std::vector<long long> t((size_t)nw * 16);
     hipMemcpy(t.data(), out, t.size() * 8, hipMemcpyDeviceToHost);
     const char *names[6] = {"stage barrier", "pass 0 tiles", "top3 + thr0", "pass 1", "barrier", "rank"};
