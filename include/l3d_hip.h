@@ -414,7 +414,7 @@ int l3d_pointwise_conv_split(const void *x, int x_mode, const void *w_split, con
  *   l3d_f16_image_bytes(kind, rows, cols)    kind 0: bytes of one plane; kind 1: of an activation image (h | m' planes + 16
  *                                            bytes: 2^-T, scratch), the activations being stored times 2^T (T per tensor: see
  *                                            conv_f16.hip); kind 2: of a split weight image of [rows = Cout][cols = Cin]
- *                                            (H | Hs | M planes + 16 bytes: 2^-S, scratch)
+ *                                            (H | Hs | M planes + 16 bytes of maxima + 2^-S_r per row r: one exponent per row)
  *   l3d_conv_f16_split_weights               w [Cout][Cin] fp32 (device) -> that image (device); two small launches
  *   l3d_split_f16_rows                       x [rows][C] fp32, or [B][C][Npts] with channel_first -> activation image
  *   l3d_pointwise_conv_f16                   y[b][co][n] = act(scale[co] sum_k w[co][k] x[b][n][k] + shift[(b,)co]);
@@ -461,7 +461,8 @@ int l3d_pointwise_conv_f16(const void *x_planes, const void *w_planes, const flo
                            const float *residual, void *out_img, const float *obs, float *ypool, int pool,
                            void *amax_out, int amax_cdiv, l3d_stream_t stream);
 /* One operand of a training-path product on the f16x2 kernel (an nn.Linear over rows, utils/transformer.py:183-189 of the reference, and
- * its dgrad): x [rows][C] fp32 with row stride `row_stride` -> fp16 planes h | m of x 2^T, UNSCALED residual, T from the window's maximum.
+ * its dgrad): x [rows][C] fp32 with row stride `row_stride` -> fp16 planes h | m of x 2^T, UNSCALED residual; T from the window's maximum
+ * (kind 0) or from each row's own maximum (kind 1: the image's per-row exponents).
  * kind 0: an activation image (l3d_f16_image_bytes(1, rows, C)); kind 1: the two planes in the slots of a weight image
  * (l3d_f16_image_bytes(2, rows, C)), i.e. the w_planes operand of l3d_pointwise_conv_f16 with L3D_CONV_F16_TWO_PLANE.  With the batch's
  * rows as w_planes (kind 1), the layer's [Cout][Cin] matrix as x_planes (kind 0), B = 1, "Cout" = rows, "N" = Cout and

@@ -31,7 +31,9 @@ static inline int l3d_divup(long a, long b) { return (int)((a + b - 1) / b); }
 // sizes of the f16x2 plane images (conv_f16.hip; exported as l3d_f16_image_bytes(kind, rows, cols))
 static inline size_t l3d_f16_plane_bytes(long rows, int cols) { return (size_t)((cols + 7) / 8) * (size_t)rows * 16; }   // one plane, tiled layout
 static inline size_t l3d_f16_act_bytes(long rows, int cols) { return 2 * l3d_f16_plane_bytes(rows, cols) + 16; }         // h | m' + {2^-T, scratch}
-static inline size_t l3d_conv_f16_weight_bytes(int Cout, int Cin) { return 3 * l3d_f16_plane_bytes(Cout, Cin) + 16; }    // H | Hs | M + {2^-S, maxima}
+// weight image: H | Hs | M planes + 16 bytes {scratch, |w| maximum, row-sum maximum} + 2^-S_r for every row r (one exponent PER ROW: a row
+// far below the matrix's largest keeps its own fp32-level precision; a shared exponent left its residual plane subnormal)
+static inline size_t l3d_conv_f16_weight_bytes(int Cout, int Cin) { return 3 * l3d_f16_plane_bytes(Cout, Cin) + 16 + (((size_t)Cout * 4 + 15) & ~(size_t)15); }
 
 // -------------------------------------------------------------------------------------------
 // Per-lane sorted top-K list kept entirely in VGPRs (K is a compile-time constant so every

@@ -4,8 +4,12 @@
 //
 // Arithmetic (see edgeconv_f16.hip for the derivation and the error measurements):
 //   activation x:  X = x 2^T (T per tensor),  h = f16(X),  m' = f16((X - h) 2^12)
-//   weight     w:  W = w 2^S (S per matrix, max|W| in [4,8)),  H = f16(W),  Hs = f16(H 2^-12),  M = f16(W - H)
+//   weight     w:  W = w 2^S (S per ROW, max_k |W_rk| in [4,8)),  H = f16(W),  Hs = f16(H 2^-12),  M = f16(W - H)
 //   acc = sum_k ( M h + Hs m' + H h ) = 2^(S+T) w.x,     y = act(acc * (scale 2^-S 2^-T) + shift)
+// S is per output row because M is not scaled: below 2^-14 it is an fp16 subnormal with a fixed absolute error of 2^-25, and with
+// one exponent for the whole matrix a row 10^-4 of the matrix's largest weight kept only ~2^-13 relative precision (its output's
+// error 150 - 660x the fp32 kernel's; tests/test_f16x2_shared_exponent_model.py).  Per row, every row's largest weight sits in
+// [4, 8) and its output keeps fp32-level error whatever the spread across rows (BatchNorm-folded scales, near-dead filters).
 // fp16 has 30 binades: T places the tensor's largest magnitude near 2^12 (16x headroom to 65504; values 2^-26 of the
 // maximum and larger keep full relative precision, smaller ones an absolute error of 2^-49 of the maximum).  The
 // generic splitter takes T from the tensor's own maximum (one extra read pass); a fused producer takes it from what it
@@ -55,7 +59,7 @@ typedef const __attribute__((address_space(1))) void *cf_gbl_ptr_t;
 
 // ---------------------------------------------------------------------------------------------
 // Splitters.  src [R][C] fp32 row-major -> planes [ceil(C/8)][R][8] fp16 (C padded with zeros).
-//   weights: H, Hs, M of src * 2^S, S chosen on the device from max|src| (two launches: max, split); *inv = 2^-S
+//   weights: H, Hs, M of src * 2^S_r, S_r chosen on the device from row r's max|src| (two launches: row maxima, split); rinv[r] = 2^-S_r
 //   activations: h, m' ; raises *range_flag if |x| > 60000
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cf_absmax_kernel(const float *__restrict__ src, size_t n, unsigned *__restrict__ out)
@@ -105,25 +109,27 @@ __global__ __launch_bounds__(256) void cf_absmax_rows_kernel(const float *__rest
     if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
 }
 
+// plane exponents stay within [-126, 126]: a tiny non-zero maximum (1e-36, an fp32 subnormal) would otherwise ask for 2^S >= 2^128 = inf
+// (and 2^-S = 0); clamped, such a tensor is placed below its target binade -- fewer bits than the target, never inf or NaN
+__device__ __forceinline__ int cf_clamp_exp(int s) { return s < -126 ? -126 : (s > 126 ? 126 : s); }
+
 __device__ __forceinline__ int cf_scale_exp(float wmax)
 {
     if (!(wmax > 0.f) || !(wmax < INFINITY)) return 0;
     int e;
     frexpf(wmax, &e);                          // wmax = f 2^e, f in [0.5, 1)  ->  wmax 2^(3-e) in [4, 8)
-    return 3 - e;
+    return cf_clamp_exp(3 - e);
 }
 
-__global__ __launch_bounds__(256) void cf_split_w_kernel(const float *__restrict__ src, int R, int C, const unsigned *__restrict__ amax,
-                                                         uint4 *__restrict__ pH, uint4 *__restrict__ pHs, uint4 *__restrict__ pM,
-                                                         float *__restrict__ inv)
+// rinv [R]: 2^-S_r from the weight image's per-row exponents (cf_rowsum_kernel); 1 / rinv is exact (a power of two)
+__global__ __launch_bounds__(256) void cf_split_w_kernel(const float *__restrict__ src, int R, int C, const float *__restrict__ rinv,
+                                                         uint4 *__restrict__ pH, uint4 *__restrict__ pHs, uint4 *__restrict__ pM)
 {
-    const int S = cf_scale_exp(__uint_as_float(*amax));
-    const float up = ldexpf(1.0f, S);
-    if (blockIdx.x == 0 && threadIdx.x == 0) *inv = ldexpf(1.0f, -S);
     const int noct = (C + 7) / 8;
     const long id = (long)blockIdx.x * 256 + threadIdx.x;
     if (id >= (long)R * noct) return;
     const int row = (int)(id % R), o = (int)(id / R);
+    const float up = 1.0f / rinv[row];
     _Float16 H[8], Hs[8], M[8];
 #pragma unroll
     for (int e = 0; e < 8; e++) {
@@ -140,15 +146,24 @@ __global__ __launch_bounds__(256) void cf_split_w_kernel(const float *__restrict
 
 // max over rows of sum_c |w[r][c]| (float bits, atomicMax): with |x| <= X it bounds every output of the layer,
 // |y_r| <= |shift_r| + |scale_r| X sum_c |w_rc| -- what lets conv_f16_kernel write its OUTPUT as fp16 planes with a scale
-// fixed before the first tile is computed.  One wave per row.
-__global__ __launch_bounds__(256) void cf_rowsum_kernel(const float *__restrict__ src, int R, int C, unsigned *__restrict__ out)
+// fixed before the first tile is computed.  Also each row's exponent, rinv[r] = 2^-S_r.  One wave per row.
+__global__ __launch_bounds__(256) void cf_rowsum_kernel(const float *__restrict__ src, int R, int C, unsigned *__restrict__ out,
+                                                        float *__restrict__ rinv)
 {
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    float s = 0.f;
+    float s = 0.f, mx = 0.f;
     if (row < R)
-        for (int c = lane; c < C; c += 64) s += fabsf(src[(size_t)row * C + c]);
+        for (int c = lane; c < C; c += 64) {
+            const float a = fabsf(src[(size_t)row * C + c]);
+            s += a;
+            mx = fmaxf(mx, a);
+        }
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+    for (int d = 32; d > 0; d >>= 1) {
+        s += __shfl_xor(s, d, 64);
+        mx = fmaxf(mx, __shfl_xor(mx, d, 64));
+    }
+    if (lane == 0 && row < R) rinv[row] = ldexpf(1.0f, -cf_scale_exp(mx));
     __shared__ float ws[4];
     if (lane == 0) ws[threadIdx.x >> 6] = s;
     __syncthreads();
@@ -161,7 +176,21 @@ __device__ __forceinline__ int cf_act_exp(float xmax)
     if (!(xmax > 0.f) || !(xmax < INFINITY)) return 0;
     int e;
     frexpf(xmax, &e);                          // xmax = f 2^e, f in [0.5, 1)  ->  xmax 2^(12-e) in [2^11, 2^12)
-    return 12 - e;
+    return cf_clamp_exp(12 - e);
+}
+
+// 2^-T_r of every row of x [R][C] (row stride `stride`), T_r from the row's own maximum: the per-row exponents of a kind-1 operand
+// image (l3d_split_f16_operand), whose rows are the kernel's "Cout".  One wave per row.
+__global__ __launch_bounds__(256) void cf_rowinv_act_kernel(const float *__restrict__ src, long R, int C, long stride, float *__restrict__ rinv)
+{
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= R) return;                      // wave-uniform
+    float mx = 0.f;
+    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, fabsf(src[row * stride + c]));
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, 64));
+    if (lane == 0) rinv[row] = ldexpf(1.0f, -cf_act_exp(mx));
 }
 
 template <bool CFIRST>
@@ -202,13 +231,15 @@ __global__ __launch_bounds__(256) void cf_split_x_kernel(const float *__restrict
 #define CFS_STRIDE (CFS_ROWS + 1)            // cells per octet line in LDS (+1: bank spread)
 __global__ __launch_bounds__(256) void cf_split_x_cl_kernel(const float *__restrict__ src, long R, int C, const unsigned *__restrict__ amax,
                                                             uint4 *__restrict__ ph, uint4 *__restrict__ pm, float *__restrict__ inv,
-                                                            int *__restrict__ range_flag, long sstride = 0, float rs = 4096.0f)
+                                                            int *__restrict__ range_flag, long sstride = 0, float rs = 4096.0f,
+                                                            const float *__restrict__ rinv = nullptr)
 {
     if (sstride == 0) sstride = C;                 // row stride of src in floats; rs = 2^12: m' = f16((X - h) 2^12), rs = 1: unscaled residual
+                                                   // rinv: 2^-T_r per row (cf_rowinv_act_kernel) instead of the tensor's 2^-T
     __shared__ uint4 lh[CFS_OCT * CFS_STRIDE], lm[CFS_OCT * CFS_STRIDE];
     const int T = cf_act_exp(__uint_as_float(*amax));
     const float up = ldexpf(1.0f, T);
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *inv = ldexpf(1.0f, -T);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && !rinv) *inv = ldexpf(1.0f, -T);
     const int t = threadIdx.x;
     const long row0 = (long)blockIdx.x * CFS_ROWS;
     const int o0 = blockIdx.y * CFS_OCT;
@@ -222,7 +253,9 @@ __global__ __launch_bounds__(256) void cf_split_x_cl_kernel(const float *__restr
             float v[8];
 #pragma unroll
             for (int e = 0; e < 8; e++) v[e] = 0.f;
+            float upr = up;
             if (row < R && o * 8 < C) {
+                if (rinv) upr = 1.0f / rinv[row];
                 const float *p = src + (size_t)row * sstride + o * 8;
                 if (o * 8 + 8 <= C && (C & 3) == 0 && (sstride & 3) == 0) {
                     const f32x4 a = *(const f32x4 *)p, b = *(const f32x4 *)(p + 4);
@@ -235,7 +268,7 @@ __global__ __launch_bounds__(256) void cf_split_x_cl_kernel(const float *__restr
             _Float16 h[8], m[8];
 #pragma unroll
             for (int e = 0; e < 8; e++) {
-                const float x = v[e] * up;
+                const float x = v[e] * upr;
                 big = fmaxf(big, fabsf(x));
                 h[e] = (_Float16)x;
                 m[e] = (_Float16)((x - (float)h[e]) * rs);
@@ -470,7 +503,11 @@ __global__ __launch_bounds__(512) void conv_f16_kernel(const uint4 *__restrict__
 
     CFM(2)
     // ---- epilogue: D[co = 32a + (r&3) + 8(r>>2) + 4(lane>>5)][n = 32c + (lane&31)]
-    const float inv = *winv * *xinv;             // 2^-S 2^-T: exact
+    // y = ((acc (scale 2^-S_co)) 2^-T) + shift: the two powers of two applied one after the other, so that a tiny row (S_co up to 126)
+    // beside small activations (T > 23) does not flush 2^-(S_co + T) to zero; the multiplications by 2^-S_co and 2^-T are exact, the
+    // result rounds once (below fp32's normal range: as its subnormal spacing allows)
+    const float xinv0 = *xinv;                   // 2^-T
+    const float *rinv = winv + 4;                // 2^-S_co: the weight image's per-row exponents
     if (oph || ypool) {
         // (1) Output as the fp16 plane image of the NEXT f16x2 layer ([Cout/8][B N][8], h | m' of y 2^To) instead of fp32: the
         // scale is fixed from a bound, |y| <= max|shift| + max|scale| (max_r sum_c |w_rc|) max|x| with max|x| <= 2^12 2^-T
@@ -485,8 +522,9 @@ __global__ __launch_bounds__(512) void conv_f16_kernel(const uint4 *__restrict__
             float bound = fmaf(obs[1] * winv[2], 4096.0f * *xinv, obs[0]) * 1.000001f;
             int e = 0;
             if (bound > 0.f && bound < 3.0e38f) (void)frexpf(bound, &e);
-            up = ldexpf(1.f, 12 - e);
-            if (blockIdx.x == 0 && t == 0) *oinv = ldexpf(1.f, e - 12);
+            const int To = cf_clamp_exp(12 - e);
+            up = ldexpf(1.f, To);
+            if (blockIdx.x == 0 && t == 0) *oinv = ldexpf(1.f, -To);
         }
       if constexpr (!GROUP) {
         const size_t rows = (size_t)Bn * N;
@@ -499,7 +537,7 @@ __global__ __launch_bounds__(512) void conv_f16_kernel(const uint4 *__restrict__
                 float sc[4], sh[4], vmax[4];
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
-                    sc[u] = (scale ? scale[cob + u] : 1.f) * inv;
+                    sc[u] = (scale ? scale[cob + u] : 1.f) * rinv[cob + u];
                     sh[u] = shift ? shift[(size_t)b * shift_bstride + cob + u] : 0.f;
                     vmax[u] = -INFINITY;
                 }
@@ -508,7 +546,7 @@ __global__ __launch_bounds__(512) void conv_f16_kernel(const uint4 *__restrict__
                     float v[4];
 #pragma unroll
                     for (int u = 0; u < 4; u++) {
-                        v[u] = acc[a][c][4 * gq + u] * sc[u] + sh[u];
+                        v[u] = acc[a][c][4 * gq + u] * sc[u] * xinv0 + sh[u];
                         if (relu) v[u] = l3d_act(v[u], relu);
                         vmax[u] = fmaxf(vmax[u], v[u]);
                     }
@@ -554,7 +592,7 @@ __global__ __launch_bounds__(512) void conv_f16_kernel(const uint4 *__restrict__
                 float sc[4], sh[4], pv[4][4];
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
-                    sc[u] = (scale ? scale[cob + u] : 1.f) * inv;
+                    sc[u] = (scale ? scale[cob + u] : 1.f) * rinv[cob + u];
                     sh[u] = shift ? shift[(size_t)b * shift_bstride + cob + u] : 0.f;
                 }
 #pragma unroll
@@ -562,7 +600,7 @@ __global__ __launch_bounds__(512) void conv_f16_kernel(const uint4 *__restrict__
                     float v[4];
 #pragma unroll
                     for (int u = 0; u < 4; u++) {
-                        v[u] = acc[a][c][4 * gq + u] * sc[u] + sh[u];
+                        v[u] = acc[a][c][4 * gq + u] * sc[u] * xinv0 + sh[u];
                         if (relu) v[u] = l3d_act(v[u], relu);
                         pv[c][u] = v[u];
                     }
@@ -633,11 +671,11 @@ __global__ __launch_bounds__(512) void conv_f16_kernel(const uint4 *__restrict__
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int co = co0 + wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const float sc = (scale ? scale[co] : 1.f) * inv;
+            const float sc = (scale ? scale[co] : 1.f) * rinv[co];
             const float sh = (!SHIFTN && shift) ? shift[(size_t)b * shift_bstride + co] : 0.f;
 #pragma unroll
             for (int c = 0; c < 4; c++) {
-                float v = acc[a][c][r] * sc + (SHIFTN ? shn[c] : sh);
+                float v = acc[a][c][r] * sc * xinv0 + (SHIFTN ? shn[c] : sh);
                 if (relu) v = l3d_act(v, relu);
                 if constexpr (RESID) v = rb[(size_t)co * N + n0 + wn * 128 + c * 32 + (lane & 31)] + v;
                 // DGCNN's conv5 (the two-plane instantiation): 134 MB of fp32 output that nothing on the chip reads back soon.  As ordinary
@@ -714,16 +752,13 @@ extern "C" int l3d_conv_f16_split_weights(const float *w, int Cout, int Cin, voi
     hipStream_t st = (hipStream_t)stream;
     const size_t pb = l3d_f16_plane_bytes(Cout, Cin);
     unsigned char *d = (unsigned char *)dst;
-    float *inv = (float *)(d + 3 * pb);
     unsigned *amax = (unsigned *)(d + 3 * pb + 4);
-    if (hipMemsetAsync(amax, 0, 8, st) != hipSuccess) return L3D_ERR_LAUNCH;       // |w| maximum and row-sum maximum
-    const size_t n = (size_t)Cout * Cin;
-    const long nblk = l3d_divup((long)n, 256);
-    hipLaunchKernelGGL(cf_absmax_kernel, dim3((unsigned)(nblk > 256 ? 256 : nblk)), dim3(256), 0, st, w, n, amax);
-    hipLaunchKernelGGL(cf_rowsum_kernel, dim3((unsigned)l3d_divup(Cout, 4)), dim3(256), 0, st, w, Cout, Cin, amax + 1);
+    float *rinv = (float *)(d + 3 * pb + 16);
+    if (hipMemsetAsync(amax, 0, 8, st) != hipSuccess) return L3D_ERR_LAUNCH;       // (unused) and row-sum maximum
+    hipLaunchKernelGGL(cf_rowsum_kernel, dim3((unsigned)l3d_divup(Cout, 4)), dim3(256), 0, st, w, Cout, Cin, amax + 1, rinv);
     const long cells = (long)Cout * ((Cin + 7) / 8);
-    hipLaunchKernelGGL(cf_split_w_kernel, dim3((unsigned)l3d_divup(cells, 256)), dim3(256), 0, st, w, Cout, Cin, (const unsigned *)amax,
-                       (uint4 *)d, (uint4 *)(d + pb), (uint4 *)(d + 2 * pb), inv);
+    hipLaunchKernelGGL(cf_split_w_kernel, dim3((unsigned)l3d_divup(cells, 256)), dim3(256), 0, st, w, Cout, Cin, (const float *)rinv,
+                       (uint4 *)d, (uint4 *)(d + pb), (uint4 *)(d + 2 * pb));
     return l3d_check_launch();
 }
 
@@ -755,8 +790,9 @@ extern "C" int l3d_split_f16_rows(const float *x, long rows, int C, int channel_
 // One operand of a training-path GEMM (models/_rows.py: an nn.Linear over rows and its dgrad on the two-plane form of the f16x2 kernel):
 // x [rows][C] fp32 with row stride `row_stride` -> two fp16 planes h | m of x 2^T with an UNSCALED residual, T from the window's own maximum.
 //   kind 0: an activation image (l3d_f16_image_bytes(1, rows, C)): the x_planes operand of l3d_pointwise_conv_f16 with L3D_CONV_F16_TWO_PLANE
-//   kind 1: the same two planes in the slots of a WEIGHT image (l3d_f16_image_bytes(2, rows, C): H at plane 0, M at plane 2, 2^-T behind
-//           them) -- the w_planes operand of the two-plane form, which reads exactly those.  With the rows of a batch as the "weight" and
+//   kind 1: the same two planes in the slots of a WEIGHT image (l3d_f16_image_bytes(2, rows, C): H at plane 0, M at plane 2, 2^-T_r per
+//           row behind them: T from each ROW's own maximum, as a weight image's S_r) -- the w_planes operand of the two-plane form, which
+//           reads exactly those.  With the rows of a batch as the "weight" and
 //           the layer's [Cout][Cin] matrix as the "activation" the kernel's [B][Cout][N] output IS y [rows][Cout], row-major.
 extern "C" int l3d_split_f16_operand(const float *x, long rows, int C, long row_stride, int kind, void *dst, int *range_flag, l3d_stream_t stream)
 {
@@ -769,7 +805,10 @@ extern "C" int l3d_split_f16_operand(const float *x, long rows, int C, long row_
     float *inv = (float *)(d + (kind ? 3 : 2) * pb);
     unsigned *amax = (unsigned *)(inv + 1);
     if (hipMemsetAsync(inv, 0, 16, st) != hipSuccess) return L3D_ERR_LAUNCH;
-    if (row_stride == C) {
+    float *rinv = kind ? inv + 4 : nullptr;
+    if (kind) {
+        hipLaunchKernelGGL(cf_rowinv_act_kernel, dim3((unsigned)l3d_divup(rows, 4L)), dim3(256), 0, st, x, rows, C, row_stride, rinv);
+    } else if (row_stride == C) {
         const size_t n = (size_t)rows * C;
         const long nblk = l3d_divup((long)n, 4096);
         hipLaunchKernelGGL(cf_absmax_kernel, dim3((unsigned)(nblk > 2048 ? 2048 : nblk)), dim3(256), 0, st, x, n, amax);
@@ -777,7 +816,7 @@ extern "C" int l3d_split_f16_operand(const float *x, long rows, int C, long row_
         hipLaunchKernelGGL(cf_absmax_rows_kernel, dim3((unsigned)l3d_divup(rows, 64L)), dim3(256), 0, st, x, rows, C, row_stride, amax);
     }
     hipLaunchKernelGGL(cf_split_x_cl_kernel, dim3((unsigned)l3d_divup(rows, (long)CFS_ROWS), (unsigned)l3d_divup((C + 7) / 8, CFS_OCT)), dim3(256), 0,
-                       st, x, rows, C, (const unsigned *)amax, ph, pm, inv, range_flag, row_stride, 1.0f);
+                       st, x, rows, C, (const unsigned *)amax, ph, pm, inv, range_flag, row_stride, 1.0f, (const float *)rinv);
     return l3d_check_launch();
 }
 
@@ -924,8 +963,9 @@ __global__ __launch_bounds__(256) void cf_first_layer_kernel(const float *__rest
     bnd = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) * 1.000001f;
     int e = 0;
     if (bnd > 0.f && bnd < 3.0e38f) (void)frexpf(bnd, &e);
-    const float up = ldexpf(1.f, 12 - e);
-    if (blockIdx.x == 0 && blockIdx.y == 0 && t == 0) *oinv = ldexpf(1.f, e - 12);
+    const int To = cf_clamp_exp(12 - e);
+    const float up = ldexpf(1.f, To);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && t == 0) *oinv = ldexpf(1.f, -To);
     const long row = (long)blockIdx.x * 256 + t;
     const int o = blockIdx.y;
     if (row >= R) return;
@@ -1017,8 +1057,9 @@ __global__ __launch_bounds__(256) void group_first_layer_planes_kernel(const flo
         bd *= 1.000001f;
         if (bd > 0.f && bd < 3.0e38f) (void)frexpf(bd, &ex);
     }
-    const float up = ldexpf(1.f, 12 - ex);
-    if (blockIdx.x == 0 && b == 0 && t == 0) *oinv = ldexpf(1.f, ex - 12);
+    const int To = cf_clamp_exp(12 - ex);
+    const float up = ldexpf(1.f, To);
+    if (blockIdx.x == 0 && b == 0 && t == 0) *oinv = ldexpf(1.f, -To);
     const int oc = t % NO, r0 = t / NO;
     float w0[8], w1[8], w2[8], sh[8];
 #pragma unroll

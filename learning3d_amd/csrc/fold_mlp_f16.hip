@@ -2,7 +2,7 @@
 // models/pcn.py:84-101) with the conv6 GEMM as "f16x2" on the fp16 matrix cores: three fp16 MFMA products per fp32 product
 // instead of bf16x3's six, fp32-level accuracy.  Structure, tiling and the conv7 reduction are fold_mlp.hip's; what
 // changes:
-//   W6 arrives as conv_f16.hip's weight image (H | Hs | M planes of W6 2^S, l3d_conv_f16_split_weights);
+//   W6 arrives as conv_f16.hip's weight image (H | Hs | M planes of W6 2^S, S per row, l3d_conv_f16_split_weights);
 //   h5, generated while it is staged, is split into two planes h, m' of h5 2^T with T chosen PER WORKGROUP from a bound
 //   the workgroup computes itself: |h5[n][k]| <= |s5[b][k]| + sum_c |W5g[k][c]| max_tile |g[n][c]| -- no extra pass, no
 //   range flag (the bound cannot be exceeded), and powers of two cancel exactly in the epilogue;
@@ -22,8 +22,9 @@ typedef const __attribute__((address_space(1))) void *ff_gbl_ptr_t;
 #define FF_C 512                        // conv5 out = conv6 in = conv6 out
 #define FF_REGION (256 * 16 + 64)
 #define FF_BUF (8 * FF_REGION)          // W: 2 planes (H, M) x 2 octets, x: 2 planes x 2 octets
-#define FF_W7OFF (3 * FF_BUF)           // W7 as float4 (w7[0][co], w7[1][co], w7[2][co], 0) per co
-#define FF_SCR (FF_W7OFF + FF_C * 16)   // 64 floats of reduction scratch
+#define FF_W7OFF (3 * FF_BUF)           // (w7[0][co], w7[1][co], w7[2][co], b6[co]) as a float4 per co
+#define FF_SOFF (FF_W7OFF + FF_C * 16)  // 2^-S_co 2^-T per co: W6's per-row exponent and the tile's plane scale
+#define FF_SCR (FF_SOFF + FF_C * 4)     // 64 floats of reduction scratch
 #define FF_LDS (FF_SCR + 256)
 
 template <int CG>
@@ -57,8 +58,9 @@ __global__ __launch_bounds__(512) void fold_mlp_f16_kernel(const float *__restri
     const int w_lds = __builtin_amdgcn_readfirstlane(wkg * FF_REGION + (wrow & ~63) * 16);
     const int x_lds = 4 * FF_REGION + xkg * FF_REGION + xrow * 16;
 
+    // (W7[0][co], W7[1][co], W7[2][co], b6[co]) per co; W6's per-row exponents 2^-S_co go to their own table (FF_SOFF) once T is known
     for (int i = t; i < FF_C; i += 512)
-        *(float4 *)(lds + FF_W7OFF + i * 16) = make_float4(w7[i], w7[FF_C + i], w7[2 * FF_C + i], 0.f);
+        *(float4 *)(lds + FF_W7OFF + i * 16) = make_float4(w7[i], w7[FF_C + i], w7[2 * FF_C + i], b6[i]);
 
     // ---- the tile's bound on h5 and the plane scale 2^T:  hmax 2^T in [2^11, 2^12)
     float *scr = (float *)(lds + FF_SCR);
@@ -95,10 +97,13 @@ __global__ __launch_bounds__(512) void fold_mlp_f16_kernel(const float *__restri
         hmax *= 1.0000005f;                                           // the fp32 evaluation of h5 may round up past the bound's own rounding
         int e = 0;
         if (hmax > 0.f && hmax < 3.0e38f) (void)frexpf(hmax, &e);   // hmax = f 2^e, f in [0.5, 1)
-        const int T = 12 - e;
+        const int T = min(12 - e, 126);                               // a tiny bound must not make 2^T inf
         up = ldexpf(1.f, T);
-        inv = ldexpf(*winv, -T);                                      // 2^-S 2^-T: exact
+        inv = ldexpf(1.f, -T);
     }
+    // 2^-S_co 2^-T per co (read in the epilogue, many barriers later); exact unless S_co + T > 149, i.e. a row of W6 and a tile of h5
+    // whose product stays below 2^-134 -- h6 is then b6 alone, within fp32's subnormal spacing of the exact value
+    for (int i = t; i < FF_C; i += 512) ((float *)(lds + FF_SOFF))[i] = winv[4 + i] * inv;
 
     float gvu[CG];                                                    // g 2^T: the generated h5 comes out in plane units
 #pragma unroll
@@ -197,17 +202,17 @@ __global__ __launch_bounds__(512) void fold_mlp_f16_kernel(const float *__restri
 #undef FF_DMA_W
 #undef FF_STORE
 
-        // ---- conv6 epilogue + conv7: h6 = relu(acc 2^-(S+T) + b6); part[c][j] += W7[j][co] * h6[co][col c]
+        // ---- conv6 epilogue + conv7: h6 = relu(acc 2^-(S_co+T) + b6); part[c][j] += W7[j][co] * h6[co][col c]
 #pragma unroll
         for (int a = 0; a < 4; a++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const int co = co0 + wm * 128 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                const float bias = b6[co];
                 const float4 wv = *(const float4 *)(lds + FF_W7OFF + co * 16);
+                const float sinv = ((const float *)(lds + FF_SOFF))[co], bias = wv.w;
 #pragma unroll
                 for (int c = 0; c < 2; c++) {
-                    const float h = fmaxf(acc[a][c][r] * inv + bias, 0.f);
+                    const float h = fmaxf(acc[a][c][r] * sinv + bias, 0.f);
                     part[c][0] = fmaf(wv.x, h, part[c][0]);
                     part[c][1] = fmaf(wv.y, h, part[c][1]);
                     part[c][2] = fmaf(wv.z, h, part[c][2]);

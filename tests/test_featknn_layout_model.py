@@ -129,7 +129,7 @@ def test_rows_as_weight_operand_layout():
     # models/_rows.py, round 6: y [rows, Cout] = x W^T through l3d_pointwise_conv_f16 with the batch's rows as the kernel's WEIGHT operand.
     # The kernel writes y[b][co][n] at (b Cout + co) N + n for weight row co and activation row n; with B = 1, "Cout" = rows and "N" = the
     # layer's Cout that offset is row * Cout + c: row-major [rows, Cout].  The two-plane form reads the weight image's planes 0 (H) and
-    # 2 (M) and the scale behind plane 2: where l3d_split_f16_operand (kind 1) puts h, m and 2^-T.
+    # 2 (M) and the per-row scales behind plane 2: where l3d_split_f16_operand (kind 1) puts h, m and 2^-T_r.
     rows, Cout, Cin = 512, 256, 64
     rng = np.random.default_rng(0)
     x, W = rng.standard_normal((rows, Cin)), rng.standard_normal((Cout, Cin))
@@ -140,9 +140,10 @@ def test_rows_as_weight_operand_layout():
             assert abs(y_kernel[co * Cout + n] - (x @ W.T)[co, n]) < 1e-12
     plane = lambda r, c: ((c + 7) // 8) * r * 16           # common.h: l3d_f16_plane_bytes
     pb = plane(rows, Cin)
-    weight_image_bytes, act_image_bytes = 3 * pb + 16, 2 * pb + 16
+    weight_image_bytes, act_image_bytes = 3 * pb + 16 + ((4 * rows + 15) // 16) * 16, 2 * pb + 16
     h_off, m_off, inv_off = 0, 2 * pb, 3 * pb              # kind 1: the slots the two-plane kernel reads (wH, wM = wp + 2 wpb, winv = wp + 3 wpb)
-    assert inv_off + 16 == weight_image_bytes and m_off + pb == inv_off
+    rinv_off = inv_off + 16                                # 2^-T_r of every row (the weight image's per-row exponents, winv + 4)
+    assert rinv_off + 4 * rows <= weight_image_bytes and m_off + pb == inv_off
     assert (0, pb, 2 * pb) == (0, pb, act_image_bytes - 16)   # kind 0: h | m | 2^-T, an ordinary activation image
     # a cell: 8 consecutive k of one row, octet-major: [k / 8][row][8 fp16]
     cell = lambda row, k: ((k // 8) * rows + row) * 16 + (k % 8) * 2
