@@ -72,44 +72,66 @@ def stage(name):
 
 
 def bn_affine(bn):
-    """eval-mode BatchNorm as y = scale * x + shift"""
-    scale = bn.weight.detach() / torch.sqrt(bn.running_var.detach() + bn.eps)
-    shift = bn.bias.detach() - bn.running_mean.detach() * scale
+    """eval-mode BatchNorm (running statistics) as y = scale * x + shift; affine=False: weight 1, bias 0"""
+    std = torch.sqrt(bn.running_var.detach() + bn.eps)
+    scale = bn.weight.detach() / std if bn.weight is not None else 1.0 / std
+    mean_scaled = bn.running_mean.detach() * scale
+    shift = bn.bias.detach() - mean_scaled if bn.bias is not None else -mean_scaled
     return scale, shift
+
+
+def bn_state(bn):
+    """The tensors an eval-mode BatchNorm's folded form depends on, for state_key.  num_batches_tracked is there for its version: a
+    train-mode forward writes the running statistics without bumping their versions (torch's kernel and l3d_bn_finalize alike), but
+    both routes add 1 to num_batches_tracked in place, which does."""
+    if bn is None:
+        return []
+    return [bn.weight, bn.bias, bn.running_mean, bn.running_var, getattr(bn, "num_batches_tracked", None)]
+
+
+def state_key(tensors):
+    """(address, version) of every source tensor of a cached image (None for an absent one)"""
+    return tuple((t.data_ptr(), t._version) if t is not None else None for t in tensors)
+
+
+def cached(store, name, sources, build, extra=()):
+    """store[name] = build(), rebuilt whenever a source tensor's address or version changes (or `extra` does).
+    The entry keeps the sources' storage alive (detached aliases), as _OBS_CACHE does: otherwise a freed block could come back
+    under the same key with other values in it -- `module.half().float()` swaps every param.data and keeps its version, and a
+    derived tensor (a folded weight or scale) is freed when its own cache is rebuilt.  Edits through `param.data` bump no version
+    and are not seen."""
+    key = tuple(extra) + state_key(sources)
+    hit = store.get(name)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    out = build()
+    store[name] = (key, out, [t.detach() for t in sources if t is not None])
+    return out
 
 
 def fold_conv_bn(conv, bn=None):
     """conv (1x1 Conv1d/Conv2d or Linear) followed by optional eval-mode BN ->
     (w [Cout,Cin], scale [Cout] or None, shift [Cout] or None) with y = scale*(w x) + shift.
-    The result is cached on the conv module per parameter / running-statistic version: folding is five tiny
+    The result is cached on the conv module per parameter / running-statistic version (`cached`): folding is five tiny
     elementwise launches per layer, ~0.65 ms per FlowNet3D forward before this cache.  Treat the returned
     tensors as read-only."""
-    ts = [conv.weight, conv.bias]
-    if bn is not None:
-        ts += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-    key = tuple((t.data_ptr(), t._version) if t is not None else None for t in ts)
-    hit = conv.__dict__.get("_l3d_fold")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    w = conv.weight.detach().reshape(conv.weight.shape[0], -1).float().contiguous()
-    bias = conv.bias.detach().float() if conv.bias is not None else None
-    if bn is None:
-        out = (w, None, bias)
-    else:
+    def build():
+        w = conv.weight.detach().reshape(conv.weight.shape[0], -1).float().contiguous()
+        bias = conv.bias.detach().float() if conv.bias is not None else None
+        if bn is None:
+            return (w, None, bias)
         scale, shift = bn_affine(bn)
         if bias is not None:
             shift = shift + scale * bias
-        out = (w, scale.float().contiguous(), shift.float().contiguous())
-    conv.__dict__["_l3d_fold"] = (key, out)
-    return out
+        return (w, scale.float().contiguous(), shift.float().contiguous())
+    return cached(conv.__dict__, "_l3d_fold", [conv.weight, conv.bias] + bn_state(bn), build, extra=(bn is not None,))
 
 
 def _stochastic_or_batch_dependent(module):
-    """train-mode BatchNorm (batch statistics) or an active Dropout: forward is not a pure function of inputs + parameters"""
-    if not module.training:
-        return False
+    """BatchNorm on batch statistics (train mode, or no running statistics: torch normalises such a layer by the batch in eval
+    mode too) or an active Dropout: forward is not a pure function of inputs + parameters"""
     for m in module.modules():
-        if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.training:
+        if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and (m.training or m.running_mean is None):
             return True
         if isinstance(m, torch.nn.modules.dropout._DropoutNd) and m.training and m.p > 0:
             return True
@@ -528,16 +550,15 @@ class EdgeConvParams:
     rebuilt only when a parameter / running statistic changes (tensor._version) or moves device."""
 
     def __init__(self):
-        self.key = None
-        self.packed = None
+        self.cache = {}
         self.v2_ok = False
 
     def get(self, convs, bns, device):
         tensors = []
         for c, b in zip(convs, bns):
-            tensors += [c.weight, b.weight, b.bias, b.running_mean, b.running_var]
-        key = (str(device),) + tuple((t.data_ptr(), t._version) for t in tensors)
-        if key != self.key:
+            tensors += [c.weight, c.bias] + bn_state(b)
+
+        def build():
             ws, scs, shs, mags = [], [], [], []
             for c, b in zip(convs, bns):
                 w, sc, sh = fold_conv_bn(c, b)
@@ -545,7 +566,8 @@ class EdgeConvParams:
                 scs.append(sc.float().cpu().contiguous())
                 shs.append(sh.float().cpu().contiguous())
                 # expected post-ReLU magnitude of the layer (4 sigma): the f16x2 kernel places its fp16 planes by it
-                mags.append(float((4.0 * b.weight.detach().abs() + b.bias.detach().abs()).max()))
+                mags.append(float((4.0 * (b.weight.detach().abs() if b.weight is not None else torch.ones_like(sc))
+                                   + (b.bias.detach().abs() if b.bias is not None else 0.0)).max()))
             cs = [w.shape[0] for w in ws]
             nfl = lib().l3d_edgeconv_packed_floats(*cs)
             if nfl == 0:
@@ -555,10 +577,9 @@ class EdgeConvParams:
             check(lib().l3d_edgeconv_pack(arr(ws), arr(scs), arr(shs), (C.c_float * 4)(*mags), *cs, ptr(packed)),
                   "l3d_edgeconv_pack")
             # the two-plane f16x2 kernel's block is usable when every layer's weights fit its scaling window
-            self.v2_ok = bool(packed[lib().l3d_edgeconv_packed_v2_flag_index()] == 1.0)
-            self.packed = packed.to(device)
-            self.key = key
-        return self.packed
+            return packed.to(device), bool(packed[lib().l3d_edgeconv_packed_v2_flag_index()] == 1.0)
+        packed, self.v2_ok = cached(self.cache, "packed", tensors, build, extra=(str(device),))
+        return packed
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -769,30 +790,27 @@ def sa_mlp3_params(convs, bns, dev):
         return None
     # keyed like fold_conv_bn: by the parameters' and running statistics' storage and version (object ids of the folded tensors could
     # be recycled after a re-fold)
-    key = tuple((t.data_ptr(), t._version) for m in list(convs) + list(bns) for t in (m.weight, m.bias, getattr(m, "running_mean", None),
-                                                                                     getattr(m, "running_var", None)) if t is not None) + (str(dev),)
-    hit = convs[0].__dict__.get("_l3d_sa3")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    parts = []
-    c0p = 8 if c0 <= 8 else 16
-    for i, (w, sc, sh) in enumerate(folded):
-        w = w.to(dev)
-        cout, cin = w.shape
-        if i == 0 and cin < c0p:
-            w = torch.nn.functional.pad(w, (0, c0p - cin))
-            cin = c0p
-        ns = cin // 4
-        run = min(4, ns)
-        wl = w.view(cout, ns // run, run, 4).permute(3, 1, 0, 2)                           # [g][s / run][n][s % run] = w[n][4 s + g]
-        if run == 2:
-            wl = torch.nn.functional.pad(wl, (0, 0, 0, 16))                                  # 16 zero rows per (g, run): bank spread
-        parts.append(wl.contiguous().view(-1))
-        parts.append((sc if sc is not None else torch.ones(cout, device=dev)).to(dev).float().view(-1))
-        parts.append((sh if sh is not None else torch.zeros(cout, device=dev)).to(dev).float().view(-1))
-    block = torch.cat(parts).contiguous()
-    convs[0].__dict__["_l3d_sa3"] = (key, (block, c0 - 3, widths))
-    return block, c0 - 3, widths
+    sources = [t for c, b in zip(convs, bns) for t in [c.weight, c.bias] + bn_state(b)]
+
+    def build():
+        parts = []
+        c0p = 8 if c0 <= 8 else 16
+        for i, (w, sc, sh) in enumerate(folded):
+            w = w.to(dev)
+            cout, cin = w.shape
+            if i == 0 and cin < c0p:
+                w = torch.nn.functional.pad(w, (0, c0p - cin))
+                cin = c0p
+            ns = cin // 4
+            run = min(4, ns)
+            wl = w.view(cout, ns // run, run, 4).permute(3, 1, 0, 2)                           # [g][s / run][n][s % run] = w[n][4 s + g]
+            if run == 2:
+                wl = torch.nn.functional.pad(wl, (0, 0, 0, 16))                                  # 16 zero rows per (g, run): bank spread
+            parts.append(wl.contiguous().view(-1))
+            parts.append((sc if sc is not None else torch.ones(cout, device=dev)).to(dev).float().view(-1))
+            parts.append((sh if sh is not None else torch.zeros(cout, device=dev)).to(dev).float().view(-1))
+        return torch.cat(parts).contiguous(), c0 - 3, widths
+    return cached(convs[0].__dict__, "_l3d_sa3", sources, build, extra=(str(dev),))
 
 
 def sa_mlp3_fused(xyz_bn3, new_xyz_bs3, feat_bdn, idx, params):

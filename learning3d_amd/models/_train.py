@@ -189,6 +189,11 @@ class _ConvAffineAct(torch.autograd.Function):
             mode, rm, rv = 1, f32c(bn.running_mean.detach()), f32c(bn.running_var.detach())
         check(lib().l3d_bn_finalize(part_ptr, nb, Cout, n, ptr(bias_f), ptr(gamma_f), ptr(beta_f), eps, mode, float(mom), ptr(rm), ptr(rv),
                                     ptr(mean64), ptr(rstd64), ptr(gr64), ptr(scale), ptr(shift), stream_ptr()), "l3d_bn_finalize")
+        if mode == 0 and rm is not None:
+            # the kernel updated the running statistics through raw pointers: bump their versions for the caches keyed on them
+            # (nothing saved for a backward aliases them: this layer keeps mean64 / rstd64)
+            torch.autograd.graph.increment_version(rm)
+            torch.autograd.graph.increment_version(rv)
         if bn is None:
             y = z
         else:
@@ -256,7 +261,7 @@ def conv_bn_act(x, conv, bn=None, relu=True, sync=None):
     with more than one rank)."""
     if sync is None:
         sync = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-    batch_stats = bn is not None and (bn.training or not bn.track_running_stats or bn.running_mean is None)
+    batch_stats = bn is not None and (bn.training or bn.running_mean is None)     # torch.nn.BatchNorm's rule
     shp = x.shape
     x3 = x.reshape(shp[0], shp[1], -1)
     y = _ConvAffineAct.apply(x3, conv.weight, conv.bias, bn.weight if bn is not None else None,
@@ -269,7 +274,7 @@ def conv_bn_act_max(x, conv, bn=None, relu=True, sync=None):
     layer of models/dgcnn.py:34-46 (`x = relu(bn(conv(x))); x1 = x.max(dim=-1, keepdim=True)[0]`) as ONE autograd node."""
     if sync is None:
         sync = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-    batch_stats = bn is not None and (bn.training or not bn.track_running_stats or bn.running_mean is None)
+    batch_stats = bn is not None and (bn.training or bn.running_mean is None)     # torch.nn.BatchNorm's rule
     B, _, N, K = x.shape
     x3 = x.reshape(B, x.shape[1], N * K)
     y, ymax = _ConvAffineAct.apply(x3, conv.weight, conv.bias, bn.weight if bn is not None else None,

@@ -33,16 +33,14 @@ class DGCNN(torch.nn.Module):
         self._packed = _fused.EdgeConvParams()
 
     def _conv5_folded(self):
-        ts = [self.conv5.weight, self.bn5.weight, self.bn5.bias, self.bn5.running_mean, self.bn5.running_var]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        if getattr(self, "_c5key", None) != key:
+        def build():
             w, s, b = _fused.fold_conv_bn(self.conv5, self.bn5)
             w = w.float().contiguous()
             w_split = _fused.split_rows(w) if (_fused.SPLIT_BF16 and w.is_cuda) else None
             w_f16 = _fused.split_weights_f16(w) if (_fused.SPLIT_BF16 and w.is_cuda) else None
-            self._c5 = (w, s.float().contiguous(), b.float().contiguous(), w_split, w_f16)
-            self._c5key = key
-        return self._c5
+            return (w, s.float().contiguous(), b.float().contiguous(), w_split, w_f16)
+        return _fused.cached(self.__dict__, "_l3d_c5", [self.conv5.weight, self.conv5.bias] + _fused.bn_state(self.bn5), build,
+                             extra=(_fused.SPLIT_BF16,))
 
     def _pooled_route(self, num_points):
         return (_fused.gemm_arith() == "f16x2" and _fused.EDGECONV_KERNEL in (None, "f16") and _fused.SPLIT_BF16

@@ -61,34 +61,25 @@ def _mlp_stack(x, convs, bns, module, pool=False, cl_shape=None):
             cin = h.shape[1]
             for i, (conv, bn) in enumerate(zip(convs, bns)):
                 w, sc, sh = _fused.fold_conv_bn(conv, bn)
-                hit = conv.__dict__.get("_l3d_w_f16p")
-                if hit is None or hit[0] != (w.data_ptr(), w._version, cin):
-                    wp = F.pad(w, (0, cin - w.shape[1])).contiguous() if cin > w.shape[1] else w     # zero columns for zero channels
-                    hit = ((w.data_ptr(), w._version, cin), _fused.split_weights_f16(wp))
-                    conv.__dict__["_l3d_w_f16p"] = hit
+                # zero columns for zero channels
+                wimg = _fused.cached(conv.__dict__, "_l3d_w_f16p", [w], lambda: _fused.split_weights_f16(
+                    F.pad(w, (0, cin - w.shape[1])).contiguous() if cin > w.shape[1] else w), extra=(cin,))
                 if i == last:
-                    return _fused.pointwise_conv_f16(img, shp[0], shp[2], hit[1], cin, w.shape[0], sc, sh, relu=True)
-                img = _fused.pointwise_conv_f16(img, shp[0], shp[2], hit[1], cin, w.shape[0], sc, sh, relu=True, out_planes=True)
+                    return _fused.pointwise_conv_f16(img, shp[0], shp[2], wimg, cin, w.shape[0], sc, sh, relu=True)
+                img = _fused.pointwise_conv_f16(img, shp[0], shp[2], wimg, cin, w.shape[0], sc, sh, relu=True, out_planes=True)
                 cin = w.shape[0]
         for i, (conv, bn) in enumerate(zip(convs, bns)):
             w, sc, sh = _fused.fold_conv_bn(conv, bn)
             if i == 0 and cl_shape is None and h.shape[1] > w.shape[1]:
                 # the producer padded the input with zero channels to a multiple of 16 (PointNetFeaturePropogation: 259 -> 272,
                 # which moves the layer from the fp32-MFMA kernel to the matrix-core split kernels): zero weight columns to match
-                hit = conv.__dict__.get("_l3d_wpad")
-                if hit is None or hit[0] != (w.data_ptr(), w._version, h.shape[1]):
-                    hit = ((w.data_ptr(), w._version, h.shape[1]), F.pad(w, (0, h.shape[1] - w.shape[1])).contiguous())
-                    conv.__dict__["_l3d_wpad"] = hit
-                w = hit[1]
+                cin = h.shape[1]
+                w = _fused.cached(conv.__dict__, "_l3d_wpad", [w], lambda: F.pad(w, (0, cin - w.shape[1])).contiguous(), extra=(cin,))
             cl = cl_shape is not None and i == 0
             n_pts = h.shape[1] if cl else h.shape[2]
             ws = None
             if _fused.split_eligible(w.shape[1], w.shape[0], n_pts):     # bf16x3 kernel: its weight planes are cached per layer
-                hit = conv.__dict__.get("_l3d_wsplit")
-                if hit is None or hit[0] != (w.data_ptr(), w._version):
-                    hit = ((w.data_ptr(), w._version), _fused.split_rows(w))
-                    conv.__dict__["_l3d_wsplit"] = hit
-                ws = hit[1]
+                ws = _fused.cached(conv.__dict__, "_l3d_wsplit", [w], lambda: _fused.split_rows(w))
             if pool and i == last and len(shp) == 4:
                 y = _fused.pointwise_conv_maxpool(h, w, sc, sh, True, shp[3], w_split=ws, channel_last=cl)
                 if y is not None:
@@ -120,9 +111,8 @@ def _factored_first_layer(src_xyz_t, centre_xyz_t, src_feat, centre_feat, idx, o
     Cc = centre_feat.shape[1] if centre_feat is not None else 0
     if C1 % 4 or C1 > 1024 or w.shape[1] != 3 + C + Cc:
         return None
-    key = (w.data_ptr(), w._version, sc.data_ptr() if sc is not None else 0, order, C, Cc)
-    hit = conv.__dict__.get("_l3d_factored")
-    if hit is None or hit[0] != key:
+
+    def build():
         if order == 0:
             wx, wf, wc = w[:, :3], w[:, 3:3 + C], w[:, 3 + C:]
         else:
@@ -131,9 +121,9 @@ def _factored_first_layer(src_xyz_t, centre_xyz_t, src_feat, centre_feat, idx, o
         # parameter-only terms of the plane route's bound, as Python floats (one sync per parameter version)
         wxr = float(wx.abs().sum(dim=1).max())
         shmax = float(sh.abs().max()) if sh is not None else 0.0
-        hit = (key, (wf.contiguous(), wc.contiguous() if Cc else None, wx, wxr, shmax))
-        conv.__dict__["_l3d_factored"] = hit
-    wf, wc, wx, wxr, shmax = hit[1]
+        return wf.contiguous(), wc.contiguous() if Cc else None, wx, wxr, shmax
+    # keyed on the folded tensors the terms are made of (their storage kept alive by the entry), not on the scale's address alone
+    wf, wc, wx, wxr, shmax = _fused.cached(conv.__dict__, "_l3d_factored", [w, sc, sh], build, extra=(order, C, Cc))
     B, N, _ = src_xyz_t.shape
     S, K = idx.shape[1], idx.shape[2]
     # the per-point products are ordinary 1x1 convs (K times fewer rows than the grouped layer); channel-last for the gather
@@ -180,13 +170,10 @@ def _f16_stack(img, B, S, K, convs, bns):
     N, last = S * K, len(convs) - 1
     for i, (conv, bn) in enumerate(zip(convs, bns)):
         w, sc, sh = _fused.fold_conv_bn(conv, bn)
-        hit = conv.__dict__.get("_l3d_w_f16")
-        if hit is None or hit[0] != (w.data_ptr(), w._version):
-            hit = ((w.data_ptr(), w._version), _fused.split_weights_f16(w))
-            conv.__dict__["_l3d_w_f16"] = hit
+        wimg = _fused.cached(conv.__dict__, "_l3d_w_f16", [w], lambda: _fused.split_weights_f16(w))
         if i == last:
-            return _fused.pointwise_conv_f16_pool(img, B, N, hit[1], w.shape[1], w.shape[0], sc, sh, relu=True, group=K)[1]
-        img = _fused.pointwise_conv_f16(img, B, N, hit[1], w.shape[1], w.shape[0], sc, sh, relu=True, out_planes=True)
+            return _fused.pointwise_conv_f16_pool(img, B, N, wimg, w.shape[1], w.shape[0], sc, sh, relu=True, group=K)[1]
+        img = _fused.pointwise_conv_f16(img, B, N, wimg, w.shape[1], w.shape[0], sc, sh, relu=True, out_planes=True)
 
 
 def _grouped_input(src_xyz_t, centre_xyz_t, src_feat, centre_feat, idx, order, module):

@@ -108,10 +108,7 @@ class PCN(torch.nn.Module):
     def _w_f16(self, name, w):
         """f16x2 weight image of a conv's (slice of a) weight, rebuilt when the parameter changes"""
         cache = self.__dict__.setdefault("_w_f16_cache", {})
-        key = (w.data_ptr(), getattr(self, name).weight._version, str(w.device), tuple(w.shape))
-        if cache.get(name, (None,))[0] != key:
-            cache[name] = (key, _fused.split_weights_f16(w.float().contiguous()))
-        return cache[name][1]
+        return _fused.cached(cache, name, [w], lambda: _fused.split_weights_f16(w.float().contiguous()), extra=(tuple(w.shape),))
 
     def _encode_f16(self, x, channel_last):
         """The encoder (pcn.py:110-124) as a chain on the fp16 matrix cores (f16x2 arithmetic, conv_f16.hip): conv1 writes fp16
@@ -160,15 +157,14 @@ class PCN(torch.nn.Module):
             from .._lib import check, f32c, lib, ptr, stream_ptr
             w6 = self.conv6.weight.detach().reshape(512, 512)
             f16 = _fused.gemm_arith() == "f16x2"                     # conv6 as f16x2 (3 fp16 products) or bf16x3 (6 bf16)
-            key = (w6.data_ptr(), self.conv6.weight._version, str(w6.device), f16)
-            if getattr(self, "_w6_split", (None,))[0] != key:
-                w6c = w6.float().contiguous()
-                self._w6_split = (key, _fused.split_weights_f16(w6c) if f16 else _fused.split_rows(w6c))
+            w6c = w6.float().contiguous()
+            w6_img = _fused.cached(self.__dict__.setdefault("_w6_split", {}), "conv6", [w6],
+                                   lambda: _fused.split_weights_f16(w6c) if f16 else _fused.split_rows(w6c), extra=(f16,))
             g_, ce = f32c(x5), f32c(center)
             B, Nf, _ = g_.shape
             out = torch.empty((B, Nf, 3), dtype=torch.float32, device=g_.device)
             fn, name = (lib().l3d_fold_mlp_f16, "l3d_fold_mlp_f16") if f16 else (lib().l3d_fold_mlp, "l3d_fold_mlp")
-            check(fn(ptr(g_), 5, ptr(f32c(w5[:, :5])), ptr(f32c(shift)), ptr(self._w6_split[1]),
+            check(fn(ptr(g_), 5, ptr(f32c(w5[:, :5])), ptr(f32c(shift)), ptr(w6_img),
                      ptr(f32c(self.conv6.bias.detach())), ptr(f32c(self.conv7.weight.detach().reshape(3, 512))),
                      ptr(f32c(self.conv7.bias.detach())), ptr(ce), B, Nf, ptr(out), stream_ptr()), name)
             return out

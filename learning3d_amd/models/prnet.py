@@ -46,23 +46,19 @@ class DGCNN(torch.nn.Module):
     def _layer_params(self, name, conv, bn, stacked):
         """BN-folded weights, cached per parameter version.  stacked: [s*W_nbr ; s*W_ctr] [2*Cout, C] and the
         shift [0 ; t];  else the plain folded conv (conv5)."""
-        ts = [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        hit = self._folded.get(name)
-        if hit is None or hit[0] != key:
+        def build():
             w, s, t = _fused.fold_conv_bn(conv, bn)
             w = (w.float() * s.float()[:, None])
             if stacked:
                 c = w.shape[1] // 2
                 w = torch.cat([w[:, :c], w[:, c:]], dim=0).contiguous()
                 t = torch.cat([torch.zeros_like(t), t]).float().contiguous()
-                hit = (key, w, t, None)
-            else:
-                w = w.contiguous()
-                w_split = _fused.split_rows(w) if (_fused.SPLIT_BF16 and w.is_cuda) else None
-                hit = (key, w, t.float().contiguous(), w_split)
-            self._folded[name] = hit
-        return hit[1:]
+                return w, t, None
+            w = w.contiguous()
+            w_split = _fused.split_rows(w) if (_fused.SPLIT_BF16 and w.is_cuda) else None
+            return w, t.float().contiguous(), w_split
+        return _fused.cached(self._folded, name, [conv.weight, conv.bias] + _fused.bn_state(bn), build,
+                             extra=(stacked, _fused.SPLIT_BF16))
 
     def forward(self, x):
         return _fused.checkpointed(self, self._forward, x)

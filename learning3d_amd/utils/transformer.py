@@ -89,43 +89,39 @@ def _linear_cf(lin, x, channel_last, relu=False, out_scale=None, planes=None, ou
         nb_, np_ = (x.size(0), x.size(1)) if img is not None else (0, 0)
     if img is not None and _fused.gemm_arith() == "f16x2" and _fused.f16_eligible(lin.in_features, lin.out_features, np_):
         # x is a LayerNorm output that came with its fp16 plane image: f16x2 kernel, no pass over x
-        key = (lin.weight.data_ptr(), lin.weight._version, str(lin.weight.device))
-        c16 = getattr(lin, "_l3d_split_f16", None)
-        if c16 is None or c16[0] != key:
-            c16 = (key, _fused.split_weights_f16(lin.weight.detach().float().contiguous()))
-            lin._l3d_split_f16 = c16
+        c16 = _fused.cached(lin.__dict__, "_l3d_split_f16", [lin.weight],
+                            lambda: _fused.split_weights_f16(lin.weight.detach().float().contiguous()))
         bias = lin.bias.detach() if lin.bias is not None else None
         scale = None
         if out_scale is not None:
             scale = torch.full((lin.out_features,), float(out_scale), dtype=torch.float32, device=img.device)
             bias = bias * float(out_scale) if bias is not None else None
         if out_planes:
-            return (_fused.pointwise_conv_f16(img, nb_, np_, c16[1], lin.in_features, lin.out_features, scale, bias, relu=relu,
+            return (_fused.pointwise_conv_f16(img, nb_, np_, c16, lin.in_features, lin.out_features, scale, bias, relu=relu,
                                               out_planes=True, unscaled=two_plane), nb_, np_)
         if amax is not None and amax[1] % 256 == 0 and PROJECTION_MAXIMA:
-            y = _fused.pointwise_conv_f16(img, nb_, np_, c16[1], lin.in_features, lin.out_features, scale, bias, relu=relu, amax=amax,
+            y = _fused.pointwise_conv_f16(img, nb_, np_, c16, lin.in_features, lin.out_features, scale, bias, relu=relu, amax=amax,
                                           unscaled=two_plane)
             y._l3d_amax = True
             return y
-        return _fused.pointwise_conv_f16(img, nb_, np_, c16[1], lin.in_features, lin.out_features, scale, bias, relu=relu,
+        return _fused.pointwise_conv_f16(img, nb_, np_, c16, lin.in_features, lin.out_features, scale, bias, relu=relu,
                                          residual=residual, unscaled=two_plane)
     if out_planes:
         return None
     if residual is not None:
         raise RuntimeError("_linear_cf: the residual epilogue exists on the f16x2 plane route only")
     x = _ln_values(x)
-    key = (lin.weight.data_ptr(), lin.weight._version, str(lin.weight.device))
-    cache = getattr(lin, "_l3d_split", None)
-    if cache is None or cache[0] != key:
+
+    def split():
         w = lin.weight.detach().float().contiguous()
-        cache = (key, w, _fused.split_rows(w))
-        lin._l3d_split = cache
+        return w, _fused.split_rows(w)
+    w, ws = _fused.cached(lin.__dict__, "_l3d_split", [lin.weight], split)
     bias = lin.bias.detach() if lin.bias is not None else None
     scale = None
     if out_scale is not None:
         scale = torch.full((lin.out_features,), float(out_scale), dtype=torch.float32, device=x.device)
         bias = bias * float(out_scale) if bias is not None else None
-    return _fused.pointwise_conv(x, cache[1], scale, bias, relu=relu, channel_last=channel_last, w_split=cache[2])
+    return _fused.pointwise_conv(x, w, scale, bias, relu=relu, channel_last=channel_last, w_split=ws)
 
 
 def clones(module, N):
@@ -247,19 +243,19 @@ class MultiHeadedAttention(nn.Module):
     def _fused_linear(self, lo, hi):
         """nn.Linear whose weight / bias are linears[lo:hi] stacked (cached per parameter version): the
         projections of one input become a single 1x1-conv launch."""
+        from ..models import _fused
         ps = [p for l in self.linears[lo:hi] for p in (l.weight, l.bias)]
-        key = (lo, hi) + tuple((p.data_ptr(), p._version) for p in ps)
-        cache = getattr(self, "_l3d_fused", {})
-        if cache.get((lo, hi), (None,))[0] != key:
+
+        def build():
             lin = nn.Linear(self.linears[lo].in_features, sum(l.out_features for l in self.linears[lo:hi]),
                             device=self.linears[lo].weight.device)
             with torch.no_grad():
                 lin.weight.copy_(torch.cat([l.weight for l in self.linears[lo:hi]], 0))
                 lin.bias.copy_(torch.cat([l.bias for l in self.linears[lo:hi]], 0))
             lin.requires_grad_(False)
-            cache[(lo, hi)] = (key, lin)
-            object.__setattr__(self, "_l3d_fused", cache)          # not a registered submodule: state_dict unchanged
-        return cache[(lo, hi)][1]
+            return lin
+        # a plain dict in the instance's __dict__, not a registered submodule: state_dict unchanged
+        return _fused.cached(self.__dict__.setdefault("_l3d_fused", {}), (lo, hi), ps, build)
 
     def forward(self, query, key, value, mask=None):
         if mask is not None:
