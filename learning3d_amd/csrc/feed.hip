@@ -9,6 +9,7 @@
 //                        R = Rotation.from_euler('zyx', [az, ay, ax]) = Rx(ax) Ry(ay) Rz(az) (extrinsic z, y, x),
 //                        evaluated in fp64 like scipy and rounded to fp32 once.
 #include "common.h"
+#include "se3_exp.h"
 
 __device__ __forceinline__ unsigned feed_mix(unsigned long long x)
 {
@@ -79,31 +80,7 @@ extern "C" int l3d_euler_transform(const float *tmpl, const float *euler_zyx, co
 //   gt = se3.exp(-x)                                                                         = the reference's `gt`
 //   source = R template + p.   Evaluated in fp64, rounded to fp32 once.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void feed_se3_exp(const double w[3], const double v[3], double R[3][3], double p[3])
-{
-    const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], t = sqrt(t2);
-    double s1, s2, s3;
-    if (t < 0.01) {                                  // ops/sinc.py:14, :100, :129
-        s1 = 1 - t2 / 6 * (1 - t2 / 20 * (1 - t2 / 42));
-        s2 = 0.5 * (1 - t2 / 12 * (1 - t2 / 30 * (1 - t2 / 56)));
-        s3 = 1.0 / 6 * (1 - t2 / 20 * (1 - t2 / 42 * (1 - t2 / 72)));
-    } else {
-        s1 = sin(t) / t;
-        s2 = (1 - cos(t)) / t2;
-        s3 = (t - sin(t)) / (t2 * t);
-    }
-    const double W[3][3] = {{0, -w[2], w[1]}, {w[2], 0, -w[0]}, {-w[1], w[0], 0}};
-    double S[3][3];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) S[i][j] = W[i][0] * W[0][j] + W[i][1] * W[1][j] + W[i][2] * W[2][j];
-    for (int i = 0; i < 3; i++) {
-        p[i] = 0;
-        for (int j = 0; j < 3; j++) {
-            R[i][j] = (i == j ? 1.0 : 0.0) + s1 * W[i][j] + s2 * S[i][j];
-            p[i] += ((i == j ? 1.0 : 0.0) + s2 * W[i][j] + s3 * S[i][j]) * v[j];
-        }
-    }
-}
+// feed_se3_exp: se3_exp.h (shared with registration.hip)
 
 __global__ __launch_bounds__(256) void twist_transform_kernel(const float *__restrict__ tmpl, const float *__restrict__ twist, int N,
                                                               float *__restrict__ source, float *__restrict__ igt, float *__restrict__ gt)

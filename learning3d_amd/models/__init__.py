@@ -6,3 +6,5 @@ from .classifier import Classifier
 from .pcn import PCN
 from .dcp import DCP
 from .flownet3d import FlowNet3D, PointNetSetAbstraction, FlowEmbedding, PointNetSetUpConv, PointNetFeaturePropogation
+from .pointnetlk import PointNetLK
+from .pcrnet import iPCRNet
