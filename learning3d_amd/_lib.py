@@ -124,6 +124,9 @@ SIGNATURES = {
     "l3d_reg_jac_pinv": [_P, _P, _P, _I, _I, _P, _P, _P],
     "l3d_reg_iclk_step": [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P],
     "l3d_reg_quat_update": [_P, _I, _I, _P, _P, _P, _P],
+    # include/l3d_curvenet.h (curvenet.hip)
+    "l3d_curve_prepare": [_P, _P, _I, _I, _I, _P, _P, _P],
+    "l3d_curve_walk": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 _RESTYPE = {"l3d_status_string": C.c_char_p, "l3d_edgeconv_packed_floats": _SZ, "l3d_split_bytes": _SZ,
             "l3d_soft_correspondence_workspace_floats": _SZ, "l3d_layernorm_backward_workspace_floats": _SZ, "l3d_knn_feature_workspace_bytes": _SZ,

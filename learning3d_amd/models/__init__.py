@@ -8,3 +8,4 @@ from .dcp import DCP
 from .flownet3d import FlowNet3D, PointNetSetAbstraction, FlowEmbedding, PointNetSetUpConv, PointNetFeaturePropogation
 from .pointnetlk import PointNetLK
 from .pcrnet import iPCRNet
+from .curvenet import CurveNet

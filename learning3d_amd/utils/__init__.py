@@ -12,4 +12,5 @@ from .model_common_utils import (
 )
 from .ppfnet_util import angle_difference, pc_normalize, sample_and_group, sample_and_group_multi
 from .pointconv_util import PointConvDensitySetAbstraction
+from .curvenet_util import LPFA, CIC
 from . import pointconv_util, pointnet2_utils
