@@ -520,7 +520,7 @@ def test_prnet_dgcnn_dynamic_graphs_golden(golden):
         out2 = net(x)
     np.testing.assert_allclose(out2.detach().cpu().numpy(), g["out"], rtol=1e-4, atol=2e-5)
     out2.sum().backward()
-    assert x.grad is not None and torch.isfinite(x.grad).all()
+    assert x.grad is not None and torch.isfinite(x.grad).all()            # its value against fp64: tests/test_gpu_grad_modules.py
     # full size (N = 1024, emb 512: feature kNN at C = 64 / 64 / 128, layers 3-4 on the GEMM kernels) against the REFERENCE class
     # run on CPU with the same seeded weights (golden prnet_dgcnn_full: every 8th channel x every 4th point, and every
     # channel's sum / maximum over the points).  A neighbour swapped at a rounding-level tie of the feature-space distances
