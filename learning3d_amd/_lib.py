@@ -1,141 +1,108 @@
-"""ctypes binding of libl3d_hip.so (the C ABI declared in include/l3d_hip.h).
+"""ctypes binding of libl3d_hip.so (the C ABI declared in include/*.h).
+
+The headers are the one description of that boundary: the prototypes, the integer #defines and the l3d_status enum are parsed
+from them when this module is imported (SIGNATURES, PROTOTYPES, CONSTANTS), and `call` is the one launch path built on them.
 
 The product path has NO fallback: if the shared library is missing, fails to load, or a call
 returns a non-zero status, this module raises.  PyTorch is used only for device memory
 (`tensor.data_ptr()`), streams (`torch.cuda.current_stream()`) and torch.distributed.
 """
 import ctypes as C
+import glob
 import os
+import re
+from collections import namedtuple
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # L3D_LIB_PATH: a library built from the same sources with other -D flags (tools/build_variant_lib.py: A/B runs of bench.py on one box)
 LIB_PATH = os.environ.get("L3D_LIB_PATH") or os.path.join(_HERE, "libl3d_hip.so")
+INCLUDE_DIR = os.path.join(_HERE, "..", "include")
 _lib = None
-
-_P, _I, _F, _SZ, _L, _D = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_long, C.c_double
-
-# name -> argtypes (restype is int unless listed in _RESTYPE)
-SIGNATURES = {
-    "l3d_version": [],
-    "l3d_status_string": [_I],
-    "l3d_last_hip_error": [],
-    "l3d_knn_graph": [_P, _I, _I, _I, _P, _P],
-    "l3d_knn_graph_variant": [_P, _I, _I, _I, _P, _I, _P],
-    "l3d_knn_feature_workspace_bytes": [_I, _I, _I],
-    "l3d_knn_feature": [_P, _I, _I, _I, _I, _P, _P, _P],
-    "l3d_lpfa_group": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
-    "l3d_graph_feature": [_P, _P, _I, _I, _I, _I, _P, _P],
-    "l3d_chamfer_forward": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
-    "l3d_chamfer_forward_variant": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
-    "l3d_chamfer_backward": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "l3d_chamfer_backward_variant": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P],
-    "l3d_chamfer_partials": [_P, _P, _I, _I, _I, _P, _P],
-    "l3d_chamfer_combine": [_P, _I, _P, _P],
-    "l3d_chamfer_loss_local_ws_bytes": [],
-    "l3d_chamfer_loss_local_mb": [_P, _P, _I, _I, _I, _P, _P, _P, _P],
-    "l3d_chamfer_forward_loss_ws_bytes": [_I, _I, _I],
-    "l3d_chamfer_forward_loss": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
-    "l3d_ball_query": [_I, _I, _I, _F, _I, _P, _P, _P, _P, _P],
-    "l3d_group_points": [_I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "l3d_group_points_grad": [_I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "l3d_group_concat": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
-    "l3d_group_concat2": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "l3d_group_first_layer": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
-    "l3d_absmax4_partials": [_P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, _P],
-    "l3d_group_first_layer_planes_auto": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _F, _F, _P, _P, _P],
-    "l3d_scatter_add_det_workspace_bytes": [_I, _I, _I],
-    "l3d_scatter_add_det": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
-    "l3d_edge_gather_max": [_P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
-    "l3d_gather_points": [_I, _I, _I, _I, _P, _P, _P, _P],
-    "l3d_gather_points_grad": [_I, _I, _I, _I, _P, _P, _P, _P],
-    "l3d_furthest_point_sampling": [_I, _I, _I, _P, _P, _P, _P],
-    "l3d_knn": [_I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "l3d_knn_variant": [_I, _I, _I, _I, _P, _P, _P, _P, _I, _P],
-    "l3d_three_nn": [_I, _I, _I, _P, _P, _P, _P, _P],
-    "l3d_three_interpolate": [_I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "l3d_three_interpolate_concat": [_I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P],
-    "l3d_three_interpolate_grad": [_I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "l3d_square_distance": [_P, _P, _I, _I, _I, _I, _P, _P],
-    "l3d_gaussian_density": [_P, _I, _I, _F, _P, _P],
-    "l3d_query_ball_point": [_F, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P],
-    "l3d_index_points": [_P, _P, _I, _I, _I, _I, _P, _P],
-    "l3d_farthest_point_sample": [_P, _I, _I, _I, _P, _P, _P, _P],
-    "l3d_knn_point": [_I, _P, _P, _I, _I, _I, _P, _P, _P],
-    "l3d_knn_point_expanded": [_I, _P, _P, _I, _I, _I, _P, _P],
-    "l3d_kabsch": [_P, _P, _I, _I, _P, _P, _P, _P],
-    "l3d_svd3x3_rotation": [_P, _I, _P, _P],
-    "l3d_soft_correspondence_workspace_floats": [_I, _I, _I],
-    "l3d_layernorm_backward_workspace_floats": [C.c_long, _I],
-    "l3d_layernorm_ref_backward": [_P, _P, _P, _F, C.c_long, _I, _P, _P, _P, _P, _P],
-    "l3d_soft_correspondence": [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P],
-    "l3d_attention_forward_strided": [_P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _F, _P, _P],
-    "l3d_attention_forward_f16b": [_P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _F, _P, _I, _P, _P, _P],
-    "l3d_sa_mlp3_fused": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "l3d_bmm_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _I, _P, _P],
-    "l3d_softmax_rows": [_P, _P, _L, _I, _F, _P, _P],
-    "l3d_split_f16_operand": [_P, _L, _I, _L, _I, _P, _P, _P],
-    "l3d_colsum_rows_workspace_bytes": [_L, _I],
-    "l3d_colsum_rows": [_P, _L, _I, _L, _P, _P, _P],
-    "l3d_layernorm_planes": [_P, _P, _P, _F, _L, _I, _P, _P, _P],
-    "l3d_add_transposed": [_P, _P, _I, _I, _I, _P, _P],
-    "l3d_max_last": [_P, _L, _I, _P, _P, _P],
-    "l3d_bn_finalize": [_P, _I, _I, _D, _P, _P, _P, _D, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P],
-    "l3d_bn_backward_finalize": [_P, _I, _P, _I, _I, _D, _I, _P, _P, _P, _P, _P, _P, _P],
-    "l3d_max_last_backward": [_P, _P, _L, _I, _P, _P],
-    "l3d_linear_rows": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
-    "l3d_layernorm_planes_cf": [_P, _P, _P, _F, _I, _I, _I, _P, _P, _I, _P],
-    "l3d_edgeconv_packed_floats": [_I, _I, _I, _I],
-    "l3d_edgeconv_pack": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "l3d_edgeconv_forward": [_P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P],
-    "l3d_edgeconv_forward_split": [_P, _P, _I, _I, _I, _P, _P, _P],
-    "l3d_edgeconv_forward_f16b": [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P],
-    "l3d_edgeconv_packed_v2_flag_index": [],
-    "l3d_pointwise_conv": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "l3d_split_bytes": [_I, _I],
-    "l3d_split_rows": [_P, _I, _I, _P, _P],
-    "l3d_pointwise_conv_split": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "l3d_f16_image_bytes": [_I, _L, _I],
-    "l3d_conv_f16_split_weights": [_P, _I, _I, _P, _P],
-    "l3d_split_f16_rows": [_P, _L, _I, _I, _I, _P, _P, _P],
-    "l3d_pointwise_conv_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P],
-    "l3d_first_layer_f16_planes": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
-    "l3d_fold_mlp": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
-    "l3d_fold_mlp_f16": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
-    "l3d_channel_stats": [_P, _I, _I, _L, _P, _P],
-    "l3d_bn_act_forward": [_P, _P, _P, _I, _I, _L, _I, _P, _P],
-    "l3d_bn_backward_stats": [_P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _P, _P, _P, _I, _P],
-    "l3d_bn_act_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _P, _P, _P, _I, _P],
-    "l3d_sum_clouds_f64": [_P, _I, _L, _P, _P],
-    "l3d_wgrad_workspace_bytes": [_I, _I, _I, _L, _I],
-    "l3d_wgrad": [_P, _P, _I, _I, _I, _L, _I, _P, _P, _P],
-    "l3d_uniform_clouds": [C.c_ulonglong, _I, _I, _F, _F, _P, _P],
-    "l3d_euler_transform": [_P, _P, _P, _I, _I, _P, _P, _P],
-    "l3d_twist_transform": [_P, _P, _I, _I, _P, _P, _P, _P],
-    "l3d_quat_transform": [_P, _P, _I, _I, _P, _P],
-    "l3d_sceneflow_batch": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "l3d_emd_workspace_bytes": [_I, _I, _I],
-    "l3d_probe_mfma_sustained": [_I, _P, _P, _P],
-    "l3d_emd_forward": [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P],
-    "l3d_emd_backward": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
-    # include/l3d_registration.h (registration.hip)
-    "l3d_reg_pose_first_layer": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P],
-    "l3d_reg_jac_pinv": [_P, _P, _P, _I, _I, _P, _P, _P],
-    "l3d_reg_iclk_step": [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P],
-    "l3d_reg_quat_update": [_P, _I, _I, _P, _P, _P, _P],
-    # include/l3d_curvenet.h (curvenet.hip)
-    "l3d_curve_prepare": [_P, _P, _I, _I, _I, _P, _P, _P],
-    "l3d_curve_walk": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-}
-_RESTYPE = {"l3d_status_string": C.c_char_p, "l3d_edgeconv_packed_floats": _SZ, "l3d_split_bytes": _SZ,
-            "l3d_soft_correspondence_workspace_floats": _SZ, "l3d_layernorm_backward_workspace_floats": _SZ, "l3d_knn_feature_workspace_bytes": _SZ,
-            "l3d_scatter_add_det_workspace_bytes": _SZ, "l3d_chamfer_loss_local_ws_bytes": _SZ, "l3d_chamfer_forward_loss_ws_bytes": _SZ, "l3d_f16_image_bytes": _SZ,
-            "l3d_wgrad_workspace_bytes": _SZ, "l3d_emd_workspace_bytes": _SZ, "l3d_colsum_rows_workspace_bytes": _SZ}
 
 
 class L3DError(RuntimeError):
     pass
+
+
+# ------------------------------------------------------------------------------------------------------------
+# The headers -> prototypes.  A small, strict parser of the C the headers actually use; anything else raises.
+_SCALAR = {"int": C.c_int, "unsigned": C.c_uint, "long": C.c_long, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong,
+           "size_t": C.c_size_t, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double,
+           "l3d_stream_t": C.c_void_p}
+# element type of a pointer parameter -> the dtype a tensor passed for it must have (None: any)
+_ELEMENT = {"float": torch.float32, "double": torch.float64, "int32_t": torch.int32, "int": torch.int32, "unsigned": torch.int32,
+            "int64_t": torch.int64, "long long": torch.int64, "long": torch.int64, "void": None, "char": None, "unsigned char": None}
+_PARAM = re.compile(r"(?:const\s+)?(?P<base>[a-z0-9_]+(?: [a-z0-9_]+)*?)\s*(?P<ptr>\*\s*(?:const\s+)?)?(?P<name>\w+)\s*(?P<arr>\[\d*\])?")
+_RETURN = re.compile(r"(?:const\s+)?(?P<base>[a-z0-9_]+(?: [a-z0-9_]+)*?)\s*(?P<ptr>\*)?")
+
+_Tensor = torch.Tensor
+_NOT_TENSORS = {int, float, bool, type(None)}     # `call`: argument types already seen not to be tensors
+_BY_VALUE, _POINTERS = object(), object()         # `call`: parameters that take no tensor, beside the dtypes of _ELEMENT
+# a parameter: its C type as written (`st[4]` as `[]`), its name, the base type, and 0 = by value, 1 = pointer / array, 2 = pointer array
+Param = namedtuple("Param", "ctype name element indirection")
+Prototype = namedtuple("Prototype", "restype params")      # restype: a ctypes type; params: tuple of Param
+
+
+def _blank(m):
+    return "\n" * m.group().count("\n")                              # cut text, keep the line numbers
+
+
+def parse_header(text, where="<header>"):
+    """-> ({name: Prototype}, {NAME: int}) of one header's `ret l3d_name(params);` declarations, `#define NAME <int>` lines and
+    l3d_status enumerators.  An unknown type or a declaration of another shape raises L3DError with the header line."""
+    text = re.sub(r"/\*.*?\*/", _blank, text, flags=re.S)
+    consts = {n: int(v, 0) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?(?:0x[0-9a-fA-F]+|\d+))[ \t]*$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#ifdef __cplusplus\n.*?^[ \t]*#endif[ \t]*$", _blank, text, flags=re.S | re.M)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+
+    def fail(pos, what):
+        raise L3DError(f"{where}:{text.count(chr(10), 0, pos) + 1}: {what}")
+
+    def c_type(pattern, decl, pos):
+        m = pattern.fullmatch(decl)
+        if m is None or m["base"] not in (_ELEMENT if m["ptr"] or m.groupdict().get("arr") else _SCALAR):
+            fail(pos, f"unrecognised C type in {decl!r}")
+        return m
+
+    protos, pos = {}, 0
+    for stmt in text.split(";"):
+        start, pos = pos + len(stmt) - len(stmt.lstrip()), pos + len(stmt) + 1
+        stmt = " ".join(stmt.split())
+        enum = re.fullmatch(r"typedef enum \{(.*)\} l3d_status", stmt)
+        if enum:
+            consts.update({n: int(v, 0) for n, v in re.findall(r"(\w+) = (-?\w+)", enum[1])})
+        if "(" not in stmt:
+            continue
+        decl = re.fullmatch(r"(.*?)\b(l3d_\w+) ?\((.*)\)", stmt)
+        if decl is None:
+            fail(start, f"not a `ret l3d_name(params)` declaration: {stmt!r}")
+        ret = c_type(_RETURN, decl[1].strip(), start)
+        params = []
+        for p in ([] if decl[3].strip() == "void" else [p.strip() for p in decl[3].split(",")]):
+            m = c_type(_PARAM, p, start)
+            params.append(Param(p[:m.start("name")].strip() + ("[]" if m["arr"] else ""), m["name"], m["base"], bool(m["ptr"]) + bool(m["arr"])))
+        restype = (C.c_char_p if ret["base"] == "char" else C.c_void_p) if ret["ptr"] else _SCALAR[ret["base"]]
+        protos[decl[2]] = Prototype(restype, tuple(params))
+    return protos, consts
+
+
+def _parse_headers():
+    protos, consts = {}, {}
+    for path in sorted(glob.glob(os.path.join(INCLUDE_DIR, "*.h"))):
+        with open(path) as f:
+            p, c = parse_header(f.read(), os.path.basename(path))
+        protos.update(p)
+        consts.update(c)
+    return protos, consts
+
+
+PROTOTYPES, CONSTANTS = _parse_headers()          # name -> Prototype; L3D_* #defines and l3d_status enumerators -> int
+globals().update(CONSTANTS)                        # _lib.L3D_OK, _lib.L3D_CONV_F16_TWO_PLANE, ...
+# name -> argtypes
+SIGNATURES = {name: [_SCALAR[p.element] if p.indirection == 0 else C.c_void_p for p in proto.params] for name, proto in PROTOTYPES.items()}
+_CALLS = {}                                        # name -> what `call` needs of an entry point; filled by lib()
 
 
 def lib():
@@ -148,10 +115,14 @@ def lib():
                 "(python -m learning3d_amd.build, or __graft_entry__.build()). "
                 "learning3d_amd has no CPU / eager fallback by design.")
         handle = C.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, proto in PROTOTYPES.items():
             fn = getattr(handle, name)          # AttributeError if the ABI drifted
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPE.get(name, _I)
+            fn.argtypes = SIGNATURES[name]
+            fn.restype = proto.restype
+            # what `call` wants of a tensor passed for each parameter, worked out once: a dtype (pointer to that element type), None
+            # (pointer to anything), or that there is none: _POINTERS (a pointer array: ctypes values only), _BY_VALUE
+            wants = tuple(_BY_VALUE if p.indirection == 0 else _POINTERS if p.indirection == 2 else _ELEMENT[p.element] for p in proto.params)
+            _CALLS[name] = (fn, wants, bool(proto.params) and proto.params[-1].element == "l3d_stream_t")
         _lib = handle
     return _lib
 
@@ -224,3 +195,62 @@ def f32c(t):
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
+
+
+def _bad_argument(name, i, a, want):
+    p = PROTOTYPES[name].params[i]
+    decl = p.ctype + ("" if p.ctype.endswith("*") else " ") + p.name
+    if not p.indirection:
+        return L3DError(f"{name}: parameter `{decl}` is passed by value, got a tensor")
+    if want is _POINTERS:
+        return L3DError(f"{name}: parameter `{decl}` takes a ctypes pointer array, got a tensor")
+    return L3DError(f"{name}: parameter `{decl}` takes a {want} tensor, got {a.dtype}")
+
+
+def call(name, *args, tag="", span=None):
+    """THE launch path: l3d_<name>(*args) on the current device's current stream, status through check() under the label name + tag.
+    Per pointer parameter: None -> NULL; a ctypes value or array -> as it is; a tensor -> its data pointer, after its dtype has
+    been held against the parameter's element type in the header (float * takes float32, int32_t * int32, void * anything, ...).
+    Then the tensors go through require_gpu (entry points without a stream parameter launch nothing and work on host memory: no
+    device rule for them).  The trailing l3d_stream_t is filled in unless given.  span: a context manager entered around the
+    library call alone (a timing span: the argument handling stays outside it)."""
+    if _lib is None:
+        lib()
+    fn, wants, has_stream = _CALLS[name]
+    if len(args) != len(wants) and len(args) + has_stream != len(wants):
+        raise L3DError(f"{name}: takes {len(wants)} arguments{' (the stream may be left out)' if has_stream else ''}, got {len(args)}")
+    out, dev, same = list(args), None, True
+    for i, a in enumerate(args):
+        t = type(a)
+        if t is not _Tensor:
+            # isinstance() of a non-tensor is the slow path of torch's metaclass: each other type (int, None, a ctypes array) pays it once
+            if t in _NOT_TENSORS:
+                continue
+            if not isinstance(a, _Tensor):
+                _NOT_TENSORS.add(t)
+                continue
+        want = wants[i]
+        if a.dtype is not want and want is not None:
+            raise _bad_argument(name, i, a, want)
+        out[i] = a.data_ptr()
+        if dev is None:
+            dev = a.get_device()                                        # the GPU's index, -1 for a CPU tensor
+        elif a.get_device() != dev:
+            same = False
+    if has_stream:
+        if dev is not None and (dev < 0 or not same):
+            require_gpu(*[a for a in args if isinstance(a, _Tensor)])   # its rule, seen to be broken: it raises, with its messages
+        if len(args) < len(wants):
+            stream = torch.cuda.current_stream()
+            current = stream.device_index
+            out.append(stream.cuda_stream)
+        else:
+            current = torch.cuda.current_device() if dev is not None else None
+        if dev is not None and dev != current:
+            require_gpu(*[a for a in args if isinstance(a, _Tensor)])
+    if span is None:
+        status = fn(*out)
+    else:
+        with span:
+            status = fn(*out)
+    check(status, name + tag)

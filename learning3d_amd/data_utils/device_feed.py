@@ -7,7 +7,7 @@ l3d_uniform_clouds (seeded by (seed, batch index, element)), rigid transforms fr
 """
 import torch
 
-from .._lib import check, lib, ptr, stream_ptr
+from .._lib import call
 from ..ops.transform_functions import DCPTransform
 
 
@@ -15,7 +15,7 @@ def uniform_clouds(batch, num_points, lo=0.0, hi=1.0, seed=0, device="cuda"):
     """[batch, num_points, 3] ~ U(lo, hi) generated on `device` (reproducible in (seed, shape))."""
     out = torch.empty((batch, num_points, 3), dtype=torch.float32, device=device)
     with torch.cuda.device(out.device):
-        check(lib().l3d_uniform_clouds(int(seed), batch, num_points, float(lo), float(hi), ptr(out), stream_ptr()), "l3d_uniform_clouds")
+        call("l3d_uniform_clouds", int(seed), batch, num_points, float(lo), float(hi), out)
     return out
 
 

@@ -27,7 +27,7 @@ import os
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, stream_ptr
+from .._lib import call
 
 MODELNET_DIR = "modelnet40_ply_hdf5_2048"
 SCENEFLOW_DIR = "data_processed_maxcut_35_20k_2k_8192"
@@ -260,10 +260,8 @@ class ResidentSceneflow:
         s1 = sample1.to(torch.int32).contiguous() if sample1 is not None else None
         s2 = sample2.to(torch.int32).contiguous() if sample2 is not None else None
         with torch.cuda.device(dev):
-            check(lib().l3d_sceneflow_batch(ptr(self.p1), ptr(self.p2), ptr(self.c1), ptr(self.c2), ptr(self.flow), ptr(self.mask),
-                                            ptr(scene_idx.to(torch.int64).contiguous()), ptr(s1), ptr(s2), B, self.p1.shape[1],
-                                            self.p2.shape[1], S, ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(o[3]), ptr(o[4]), ptr(om),
-                                            stream_ptr()), "l3d_sceneflow_batch")
+            call("l3d_sceneflow_batch", self.p1, self.p2, self.c1, self.c2, self.flow, self.mask, scene_idx.to(torch.int64).contiguous(),
+                 s1, s2, B, self.p1.shape[1], self.p2.shape[1], S, *o, om)
         return o[0], o[1], o[2], o[3], o[4], om.bool()
 
     def __iter__(self):

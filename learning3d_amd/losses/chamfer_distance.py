@@ -8,7 +8,7 @@ torch broadcast when that fails (:36-42); here the native path is the only path.
 import torch
 import torch.nn as nn
 
-from .._lib import check, f32c, lib, ptr, require_gpu, stream_ptr
+from .._lib import call, f32c, lib, require_gpu
 
 
 class ChamferDistanceFunction(torch.autograd.Function):
@@ -16,7 +16,6 @@ class ChamferDistanceFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz1, xyz2):
-        require_gpu(xyz1, xyz2)
         batchsize, n, _ = xyz1.size()
         _, m, _ = xyz2.size()
         xyz1 = f32c(xyz1)
@@ -26,8 +25,7 @@ class ChamferDistanceFunction(torch.autograd.Function):
         dist2 = torch.empty(batchsize, m, dtype=torch.float32, device=dev)
         idx1 = torch.empty(batchsize, n, dtype=torch.int32, device=dev)
         idx2 = torch.empty(batchsize, m, dtype=torch.int32, device=dev)
-        check(lib().l3d_chamfer_forward(ptr(xyz1), ptr(xyz2), batchsize, n, m, ptr(dist1), ptr(dist2),
-                                        ptr(idx1), ptr(idx2), stream_ptr()), "l3d_chamfer_forward")
+        call("l3d_chamfer_forward", xyz1, xyz2, batchsize, n, m, dist1, dist2, idx1, idx2)
         ctx.save_for_backward(xyz1, xyz2, idx1, idx2)
         return dist1, dist2
 
@@ -40,9 +38,7 @@ class ChamferDistanceFunction(torch.autograd.Function):
         m = xyz2.shape[1]
         gradxyz1 = torch.empty_like(xyz1)
         gradxyz2 = torch.empty_like(xyz2)
-        check(lib().l3d_chamfer_backward(ptr(xyz1), ptr(xyz2), b, n, m, ptr(graddist1), ptr(graddist2),
-                                         ptr(idx1), ptr(idx2), ptr(gradxyz1), ptr(gradxyz2), stream_ptr()),
-              "l3d_chamfer_backward")
+        call("l3d_chamfer_backward", xyz1, xyz2, b, n, m, graddist1, graddist2, idx1, idx2, gradxyz1, gradxyz2)
         return gradxyz1, gradxyz2
 
 
@@ -54,13 +50,11 @@ class ChamferDistance(torch.nn.Module):
 def chamfer_partials(dist1, dist2):
     """Device fp64 tensor [4] = (sum sqrt(dist1), sum sqrt(dist2), #dist1, #dist2): the per-shard
     partial sums the multi-GPU path all-gathers (forward-only helper; no autograd, no host sync)."""
-    require_gpu(dist1, dist2)
     dist1, dist2 = f32c(dist1), f32c(dist2)                  # the kernels read dense fp32 with 16-byte loads
     B, N = dist1.shape
     M = dist2.shape[1]
     part = torch.empty(4, dtype=torch.float64, device=dist1.device)
-    check(lib().l3d_chamfer_partials(ptr(dist1), ptr(dist2), B, N, M, ptr(part), stream_ptr()),
-          "l3d_chamfer_partials")
+    call("l3d_chamfer_partials", dist1, dist2, B, N, M, part)
     return part
 
 
@@ -85,8 +79,7 @@ def chamfer_loss_local(dist1, dist2):
     ws = _LL_WS[key][0]
     part = torch.empty(4, dtype=torch.float64, device=dist1.device)
     loss = torch.empty((), dtype=torch.float32, device=dist1.device)
-    check(lib().l3d_chamfer_loss_local_mb(ptr(dist1), ptr(dist2), B, N, M, ptr(ws), ptr(part), ptr(loss), stream_ptr()),
-          "l3d_chamfer_loss_local_mb")
+    call("l3d_chamfer_loss_local_mb", dist1, dist2, B, N, M, ws, part, loss)
     return loss
 
 
@@ -117,8 +110,7 @@ def chamfer_forward_loss(template, source, want="loss"):
     idx2 = torch.empty(B, M, dtype=torch.int32, device=dev)
     part = torch.empty(4, dtype=torch.float64, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
-    check(lib().l3d_chamfer_forward_loss(ptr(xyz1), ptr(xyz2), B, N, M, ptr(dist1), ptr(dist2), ptr(idx1), ptr(idx2), ptr(ws),
-                                         ptr(part), ptr(loss), stream_ptr()), "l3d_chamfer_forward_loss")
+    call("l3d_chamfer_forward_loss", xyz1, xyz2, B, N, M, dist1, dist2, idx1, idx2, ws, part, loss)
     if want == "loss":
         return loss
     if want == "partials":
@@ -133,8 +125,7 @@ def chamfer_combine(partials):
         raise TypeError("chamfer_combine expects the fp64 partial sums of chamfer_partials")
     partials = partials.contiguous().view(-1, 4)
     loss = torch.empty((), dtype=torch.float32, device=partials.device)
-    check(lib().l3d_chamfer_combine(ptr(partials), partials.shape[0], ptr(loss), stream_ptr()),
-          "l3d_chamfer_combine")
+    call("l3d_chamfer_combine", partials, partials.shape[0], loss)
     return loss
 
 

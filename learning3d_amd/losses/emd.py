@@ -8,7 +8,7 @@ mean(cost)/N is what is implemented here).
 import torch
 import torch.nn as nn
 
-from .._lib import check, f32c, lib, ptr, require_gpu, stream_ptr
+from .._lib import call, f32c, lib, require_gpu
 
 
 EMD_BACKWARD_MAX_M = 10176      # emd.hip, l3d_emd_backward: (m rounded up to 64 points, + 32) float4 records in 160 KB of LDS
@@ -30,8 +30,7 @@ class EMDFunction(torch.autograd.Function):
         match = torch.empty((B, n, m), dtype=torch.float32, device=dev)
         cost = torch.empty((B,), dtype=torch.float32, device=dev)
         ws = torch.empty((lib().l3d_emd_workspace_bytes(B, n, m),), dtype=torch.uint8, device=dev)
-        check(lib().l3d_emd_forward(ptr(xyz1), ptr(xyz2), B, n, m, ptr(match), ptr(cost), ptr(ws), 0, stream_ptr()),
-              "l3d_emd_forward")
+        call("l3d_emd_forward", xyz1, xyz2, B, n, m, match, cost, ws, 0)
         ctx.save_for_backward(xyz1, xyz2, match)
         return cost
 
@@ -43,8 +42,7 @@ class EMDFunction(torch.autograd.Function):
         m = xyz2.shape[1]
         g1 = torch.empty_like(xyz1)
         g2 = torch.empty_like(xyz2)
-        check(lib().l3d_emd_backward(ptr(xyz1), ptr(xyz2), ptr(match), B, n, m, ptr(g1), ptr(g2), stream_ptr()),
-              "l3d_emd_backward")
+        call("l3d_emd_backward", xyz1, xyz2, match, B, n, m, g1, g2)
         return g1, g2
 
 

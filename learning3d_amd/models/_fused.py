@@ -16,7 +16,7 @@ import threading
 
 import torch
 
-from .._lib import check, f32c, lib, ptr, require_gpu, stream_ptr
+from .._lib import L3D_CONV_F16_OUT_UNSCALED, L3D_CONV_F16_TWO_PLANE, call, f32c, lib, ptr, require_gpu
 
 
 class _NullSpan:
@@ -288,11 +288,10 @@ SPLIT_BF16 = True
 
 def split_rows(m):
     """fp32 [rows, cols] (device) -> split + tiled bf16x3 image (uint8 tensor) for l3d_pointwise_conv_split"""
-    require_gpu(m)
     m = f32c(m)
     rows, cols = m.shape
     out = torch.empty(lib().l3d_split_bytes(rows, cols), dtype=torch.uint8, device=m.device)
-    check(lib().l3d_split_rows(ptr(m), rows, cols, ptr(out), stream_ptr()), "l3d_split_rows")
+    call("l3d_split_rows", m, rows, cols, out)
     return out
 
 
@@ -302,11 +301,10 @@ def split_eligible(Cin, Cout, N):
 
 def split_weights_f16(w):
     """fp32 [Cout, Cin] (device) -> f16x2 weight image (H | Hs | M planes + 2^-S) for l3d_pointwise_conv_f16"""
-    require_gpu(w)
     w = f32c(w)
     Cout, Cin = w.shape
     out = torch.empty(lib().l3d_f16_image_bytes(2, Cout, Cin), dtype=torch.uint8, device=w.device)
-    check(lib().l3d_conv_f16_split_weights(ptr(w), Cout, Cin, ptr(out), stream_ptr()), "l3d_conv_f16_split_weights")
+    call("l3d_conv_f16_split_weights", w, Cout, Cin, out)
     return out
 
 
@@ -321,8 +319,7 @@ def split_rows_f16(x, channel_first=False):
         B, N, C = x.shape
     rows = B * N
     out = torch.empty(lib().l3d_f16_image_bytes(1, rows, C), dtype=torch.uint8, device=x.device)
-    check(lib().l3d_split_f16_rows(ptr(x), rows, C, int(channel_first), N, ptr(out), ptr(range_flag(x.device)), stream_ptr()),
-          "l3d_split_f16_rows")
+    call("l3d_split_f16_rows", x, rows, C, int(channel_first), N, out, ptr(range_flag(x.device)))
     return out
 
 
@@ -350,17 +347,11 @@ def _plane_obs(scale, shift, dev):
     return hit[0]
 
 
-def _conv_f16(label, x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu, flags=0, y=None, residual=None, img=None,
-              obs=None, ypool=None, pool=0, amax=None, amax_cdiv=0):
-    """the one C entry point of the f16x2 layer (l3d_pointwise_conv_f16); `label` names the variant in the launch log"""
-    rc = lib().l3d_pointwise_conv_f16(ptr(x_planes), ptr(w_planes), ptr(scale), ptr(shift), bstride, B, Cin, Cout, N, int(relu),
-                                      flags, ptr(y), ptr(residual), ptr(img), ptr(obs), ptr(ypool), int(pool), ptr(amax),
-                                      int(amax_cdiv), stream_ptr())
-    check(rc, label)
-
-
-CONV_F16_TWO_PLANE = 1        # include/l3d_hip.h: L3D_CONV_F16_TWO_PLANE
-CONV_F16_OUT_UNSCALED = 2     # include/l3d_hip.h: L3D_CONV_F16_OUT_UNSCALED
+def _conv_f16(tag, x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu, flags=0, y=None, residual=None, img=None,
+              obs=None, ypool=None, pool=0, amax=None, amax_cdiv=0, span=None):
+    """the one C entry point of the f16x2 layer (l3d_pointwise_conv_f16); `tag` names the variant in the launch log"""
+    call("l3d_pointwise_conv_f16", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, int(relu), flags, y, residual, img, obs,
+         ypool, int(pool), amax, int(amax_cdiv), tag=tag, span=span)
 
 
 def pointwise_conv_f16(x_planes, B, N, w_planes, Cin, Cout, scale=None, shift=None, relu=False, out_planes=False, amax=None,
@@ -383,8 +374,8 @@ def pointwise_conv_f16(x_planes, B, N, w_planes, Cin, Cout, scale=None, shift=No
         dev = x_planes.device
         obs = _plane_obs(scale, shift, dev)
         img = torch.empty(lib().l3d_f16_image_bytes(1, B * N, Cout), dtype=torch.uint8, device=dev)
-        _conv_f16("l3d_pointwise_conv_f16[planes]" + ("[two-plane]" if two else ""), x_planes, w_planes, scale, shift, 0, B, Cin, Cout, N,
-                  relu, flags=(CONV_F16_TWO_PLANE | CONV_F16_OUT_UNSCALED) if two else 0, img=img, obs=obs)
+        _conv_f16("[planes]" + ("[two-plane]" if two else ""), x_planes, w_planes, scale, shift, 0, B, Cin, Cout, N,
+                  relu, flags=(L3D_CONV_F16_TWO_PLANE | L3D_CONV_F16_OUT_UNSCALED) if two else 0, img=img, obs=obs)
         return img
     bstride = Cout if (shift is not None and shift.dim() == 2) else 0
     y = torch.empty((B, Cout, N), dtype=torch.float32, device=x_planes.device)
@@ -392,24 +383,23 @@ def pointwise_conv_f16(x_planes, B, N, w_planes, Cin, Cout, scale=None, shift=No
         # y = residual + layer(x): the sublayer's residual connection in the GEMM's epilogue
         if amax is not None or tuple(residual.shape) != (B, Cout, N) or not (Cout % 256 == 0 and N % 256 == 0):
             raise ValueError("residual epilogue: residual [B,Cout,N], Cout % 256 == 0, N % 256 == 0, no absmax")
-        _conv_f16("l3d_pointwise_conv_f16[residual]" + ("[two-plane]" if two else ""), x_planes, w_planes, scale, shift, bstride, B, Cin,
-                  Cout, N, relu, flags=CONV_F16_TWO_PLANE if two else 0, y=y, residual=f32c(residual))
+        _conv_f16("[residual]" + ("[two-plane]" if two else ""), x_planes, w_planes, scale, shift, bstride, B, Cin,
+                  Cout, N, relu, flags=L3D_CONV_F16_TWO_PLANE if two else 0, y=y, residual=f32c(residual))
         return y
     if two and amax is not None:
-        _conv_f16("l3d_pointwise_conv_f16[absmax][two-plane]", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu,
-                  flags=CONV_F16_TWO_PLANE, y=y, amax=amax[0], amax_cdiv=int(amax[1]))
+        _conv_f16("[absmax][two-plane]", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu,
+                  flags=L3D_CONV_F16_TWO_PLANE, y=y, amax=amax[0], amax_cdiv=int(amax[1]))
         return y
     if unscaled:
         # the image's residual plane is unscaled (edgeconv_forward(..., planes=True, unscaled=True)): two weight planes
-        with stage("conv5_kernel"):
-            _conv_f16("l3d_pointwise_conv_f16[two-plane]", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu,
-                      flags=CONV_F16_TWO_PLANE, y=y)
+        _conv_f16("[two-plane]", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu, flags=L3D_CONV_F16_TWO_PLANE, y=y,
+                  span=stage("conv5_kernel"))               # the launch alone (bench.py's live timing)
         return y
     if amax is not None:
-        _conv_f16("l3d_pointwise_conv_f16[absmax]", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu, y=y,
+        _conv_f16("[absmax]", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu, y=y,
                   amax=amax[0], amax_cdiv=int(amax[1]))
         return y
-    _conv_f16("l3d_pointwise_conv_f16", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu, y=y)
+    _conv_f16("", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu, y=y)
     return y
 
 
@@ -426,8 +416,7 @@ def first_layer_f16_planes(x, w, shift, relu, channel_last):
     shift = f32c(shift) if shift is not None else None
     xmax = x.abs().max().reshape(1)
     img = torch.empty(lib().l3d_f16_image_bytes(1, B * N, Cout), dtype=torch.uint8, device=x.device)
-    check(lib().l3d_first_layer_f16_planes(ptr(x), int(channel_last), ptr(w), ptr(shift), ptr(xmax), B, Cin, Cout, N, int(relu),
-                                           ptr(img), ptr(range_flag(x.device)), stream_ptr()), "l3d_first_layer_f16_planes")
+    call("l3d_first_layer_f16_planes", x, int(channel_last), w, shift, xmax, B, Cin, Cout, N, int(relu), img, ptr(range_flag(x.device)))
     return img
 
 
@@ -450,7 +439,7 @@ def pointwise_conv_f16_pool(x_planes, B, N, w_planes, Cin, Cout, scale=None, shi
     pk = int(group) if group else 128
     if pool or group:
         part = torch.empty((B, Cout, N // pk), dtype=torch.float32, device=dev)
-    _conv_f16("l3d_pointwise_conv_f16[pool]", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu, img=img, obs=obs,
+    _conv_f16("[pool]", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu, img=img, obs=obs,
               ypool=part, pool=pk)
     if group:
         return img, part
@@ -477,12 +466,10 @@ def pointwise_conv_maxpool(x, w, scale, shift, relu, pool, w_split=None, channel
     if split_eligible(Cin, Cout, N) and N % 256 == 0:
         if w_split is None:
             w_split = split_rows(w)
-        check(lib().l3d_pointwise_conv_split(ptr(x), int(channel_last), ptr(w_split), ptr(scale), ptr(shift), bstride, B, Cin, Cout,
-                                             N, int(relu), pool, ptr(y), stream_ptr()),
-              "l3d_pointwise_conv_split[maxpool]")
+        call("l3d_pointwise_conv_split", x, int(channel_last), w_split, scale, shift, bstride, B, Cin, Cout, N, int(relu), pool, y,
+             tag="[maxpool]")
         return y
-    check(lib().l3d_pointwise_conv(ptr(x), int(channel_last), ptr(w), ptr(scale), ptr(shift), bstride, B, Cin, Cout, N, int(relu),
-                                   pool, ptr(y), stream_ptr()), "l3d_pointwise_conv[maxpool]")
+    call("l3d_pointwise_conv", x, int(channel_last), w, scale, shift, bstride, B, Cin, Cout, N, int(relu), pool, y, tag="[maxpool]")
     return y
 
 
@@ -523,12 +510,9 @@ def pointwise_conv(x, w, scale=None, shift=None, relu=False, channel_last=False,
     if use_split:
         if w_split is None:
             w_split = split_rows(w)
-        check(lib().l3d_pointwise_conv_split(ptr(x), int(channel_last), ptr(w_split), ptr(scale), ptr(shift), bstride,
-                                             B, Cin, Cout, N, int(relu), 0, ptr(y), stream_ptr()),
-              "l3d_pointwise_conv_split")
+        call("l3d_pointwise_conv_split", x, int(channel_last), w_split, scale, shift, bstride, B, Cin, Cout, N, int(relu), 0, y)
         return y
-    check(lib().l3d_pointwise_conv(ptr(x), int(channel_last), ptr(w), ptr(scale), ptr(shift), bstride, B, Cin, Cout, N,
-                                   int(relu), 0, ptr(y), stream_ptr()), "l3d_pointwise_conv")
+    call("l3d_pointwise_conv", x, int(channel_last), w, scale, shift, bstride, B, Cin, Cout, N, int(relu), 0, y)
     return y
 
 
@@ -540,7 +524,7 @@ def linear_rows(x, lin, relu=False):
     R, Cin = x.shape
     if Cin % 256 == 0:
         y = torch.empty((R, w.shape[0]), dtype=torch.float32, device=x.device)
-        check(lib().l3d_linear_rows(ptr(x), ptr(w), ptr(b), R, Cin, w.shape[0], int(relu), ptr(y), stream_ptr()), "l3d_linear_rows")
+        call("l3d_linear_rows", x, w, b, R, Cin, w.shape[0], int(relu), y)
         return y
     return pointwise_conv(x.unsqueeze(0), w, None, b, relu=relu, channel_last=True)[0].t()
 
@@ -574,8 +558,7 @@ class EdgeConvParams:
                 raise NotImplementedError(f"EdgeConv channel widths {cs} are not built (64/64/128/256 only)")
             packed = torch.empty(nfl, dtype=torch.float32)
             arr = lambda ts: (C.c_void_p * 4)(*[t.data_ptr() for t in ts])
-            check(lib().l3d_edgeconv_pack(arr(ws), arr(scs), arr(shs), (C.c_float * 4)(*mags), *cs, ptr(packed)),
-                  "l3d_edgeconv_pack")
+            call("l3d_edgeconv_pack", arr(ws), arr(scs), arr(shs), (C.c_float * 4)(*mags), *cs, packed)      # host memory, no launch
             # the two-plane f16x2 kernel's block is usable when every layer's weights fit its scaling window
             return packed.to(device), bool(packed[lib().l3d_edgeconv_packed_v2_flag_index()] == 1.0)
         packed, self.v2_ok = cached(self.cache, "packed", tensors, build, extra=(str(device),))
@@ -741,10 +724,10 @@ def edgeconv_forward(xyz_bn3, idx, packed, widths=(64, 64, 128, 256), kernel=Non
         if not (v2 and k <= 20 and tuple(widths) == (64, 64, 128, 256)):
             raise ValueError("planes output is produced by the f16 EdgeConv kernel only (usable two-plane block, k <= 20, 64/64/128/256)")
         out = torch.empty(lib().l3d_f16_image_bytes(1, B * N, sum(widths)), dtype=torch.uint8, device=xyz_bn3.device)
-        args = (ptr(xyz_bn3), ptr(idx), B, N, k, ptr(packed), ptr(out), 2 if unscaled else 1, ptr(range_flag(xyz_bn3.device)), stream_ptr())
-        with stage("edgeconv_kernel"):                   # the launch alone: a timing span here holds no Python between its
-            rc = lib().l3d_edgeconv_forward_f16b(*args)  # first event and the kernel (bench.py's live roofline timing)
-        check(rc, "l3d_edgeconv_forward_f16b")
+        # span: the launch alone -- a timing span here holds no Python between its first event and the kernel (bench.py's live
+        # roofline timing)
+        call("l3d_edgeconv_forward_f16b", xyz_bn3, idx, B, N, k, packed, out, 2 if unscaled else 1, ptr(range_flag(xyz_bn3.device)),
+             span=stage("edgeconv_kernel"))
         return out
     if unscaled:
         raise ValueError("an unscaled residual plane belongs to the plane image (planes=True)")
@@ -758,17 +741,12 @@ def edgeconv_forward(xyz_bn3, idx, packed, widths=(64, 64, 128, 256), kernel=Non
     if kernel == "f16" and not v2:
         kernel = "split"
     if kernel == "f16":
-        fn, name = lib().l3d_edgeconv_forward_f16b, "l3d_edgeconv_forward_f16b"
-        args = (ptr(xyz_bn3), ptr(idx), B, N, k, ptr(packed), ptr(pooled), 0, ptr(range_flag(xyz_bn3.device)), stream_ptr())
+        name, tail = "l3d_edgeconv_forward_f16b", (pooled, 0, ptr(range_flag(xyz_bn3.device)))
     elif kernel == "split":
-        fn, name = lib().l3d_edgeconv_forward_split, "l3d_edgeconv_forward_split"
-        args = (ptr(xyz_bn3), ptr(idx), B, N, k, ptr(packed), ptr(pooled), stream_ptr())
+        name, tail = "l3d_edgeconv_forward_split", (pooled,)
     else:
-        fn, name = lib().l3d_edgeconv_forward, "l3d_edgeconv_forward"
-        args = (ptr(xyz_bn3), ptr(idx), B, N, k, ptr(packed), *widths, ptr(pooled), stream_ptr())
-    with stage("edgeconv_kernel"):
-        rc = fn(*args)
-    check(rc, name)
+        name, tail = "l3d_edgeconv_forward", (*widths, pooled)
+    call(name, xyz_bn3, idx, B, N, k, packed, *tail, span=stage("edgeconv_kernel"))
     return pooled
 
 
@@ -822,6 +800,5 @@ def sa_mlp3_fused(xyz_bn3, new_xyz_bs3, feat_bdn, idx, params):
     x, q = f32c(xyz_bn3), f32c(new_xyz_bs3)
     f = f32c(feat_bdn) if D > 0 else None
     out = torch.empty((B, widths[2], S), dtype=torch.float32, device=x.device)
-    check(lib().l3d_sa_mlp3_fused(ptr(x), ptr(q), ptr(f), ptr(idx.contiguous()), ptr(block), B, N, S, K, D, widths[0], widths[1], widths[2],
-                                  ptr(out), stream_ptr()), "l3d_sa_mlp3_fused")
+    call("l3d_sa_mlp3_fused", x, q, f, idx.contiguous(), block, B, N, S, K, D, widths[0], widths[1], widths[2], out)
     return out

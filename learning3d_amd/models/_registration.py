@@ -1,11 +1,9 @@
 """Host side of registration.hip for the iterative registration models (pointnetlk.py, pcrnet.py): the PointNet pass whose first
 layer poses its cloud on the fly, and thin wrappers of the loop kernels.  Everything here only launches on the current stream:
 no host read, no allocation whose size depends on data, so a loop built from these calls can be captured in one graph."""
-import ctypes as C
-
 import torch
 
-from .._lib import check, f32c, lib, ptr, require_gpu, stream_ptr
+from .._lib import call, f32c, require_gpu
 from . import _fused
 from .pointnet import PointNet
 
@@ -37,8 +35,7 @@ def posed_features(feature_model, cloud, T=None, dt=None, want_features=True, wa
     C1 = w1.shape[0]
     y = torch.empty((B * Tn, C1, N), dtype=torch.float32, device=cloud.device) if want_features else None
     posed = torch.empty((B * Tn, N, 3), dtype=torch.float32, device=cloud.device) if want_cloud else None
-    check(lib().l3d_reg_pose_first_layer(ptr(cloud), ptr(T), ptr(dt), B, Tn, N, ptr(w1), ptr(sc1), ptr(sh1), C1, 1, ptr(y), ptr(posed),
-                                         stream_ptr()), "l3d_reg_pose_first_layer")
+    call("l3d_reg_pose_first_layer", cloud, T, dt, B, Tn, N, w1, sc1, sh1, C1, 1, y, posed)
     if not want_features:
         return None, posed
     x = y
@@ -47,8 +44,7 @@ def posed_features(feature_model, cloud, T=None, dt=None, want_features=True, wa
     w, sc, sh = stack[-1]
     if N % 64 == 0:
         part = torch.empty((B * Tn, w.shape[0], N // 64), dtype=torch.float32, device=cloud.device)
-        check(lib().l3d_pointwise_conv(ptr(x), 0, ptr(w), ptr(sc), ptr(sh), 0, B * Tn, w.shape[1], w.shape[0], N, 1, 64, ptr(part),
-                                       stream_ptr()), "l3d_pointwise_conv[maxpool]")
+        call("l3d_pointwise_conv", x, 0, w, sc, sh, 0, B * Tn, w.shape[1], w.shape[0], N, 1, 64, part, tag="[maxpool]")
         return part.max(dim=2)[0], posed
     return _fused.pointwise_conv(x, w, sc, sh, relu=True, split=False).max(dim=2)[0], posed
 
@@ -57,19 +53,17 @@ def jac_pinv(f0, f, dt, singular):
     """f0 [B,K], f [B 6,K], dt [6], singular int32 [1 + B] (zeroed) -> pinv [B,6,K]"""
     B, K = f0.shape
     pinv = torch.empty((B, 6, K), dtype=torch.float32, device=f0.device)
-    check(lib().l3d_reg_jac_pinv(ptr(f0), ptr(f), ptr(dt), B, K, ptr(pinv), ptr(singular), stream_ptr()), "l3d_reg_jac_pinv")
+    call("l3d_reg_jac_pinv", f0, f, dt, B, K, pinv, singular)
     return pinv
 
 
 def iclk_step(f, f0, pinv, step, maxiter, xtol, singular, ws, state, est_T, series, r):
     B, K = f0.shape
-    check(lib().l3d_reg_iclk_step(ptr(f), ptr(f0), ptr(pinv), B, K, step, maxiter, float(xtol), ptr(singular), ptr(ws), ptr(state),
-                                  ptr(est_T), ptr(series), ptr(r), stream_ptr()), "l3d_reg_iclk_step")
+    call("l3d_reg_iclk_step", f, f0, pinv, B, K, step, maxiter, float(xtol), singular, ws, state, est_T, series, r)
 
 
 def quat_update(pose7, first, est_R, est_t, est_T):
-    check(lib().l3d_reg_quat_update(ptr(pose7), pose7.shape[0], int(first), ptr(est_R), ptr(est_t), ptr(est_T), stream_ptr()),
-          "l3d_reg_quat_update")
+    call("l3d_reg_quat_update", pose7, pose7.shape[0], int(first), est_R, est_t, est_T)
 
 
 def prepare(*clouds):

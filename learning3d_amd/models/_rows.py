@@ -12,7 +12,7 @@ import os
 
 import torch
 
-from .._lib import check, f32c, lib, on_device_of, ptr, stream_ptr
+from .._lib import L3D_CONV_F16_SHIFT_N, L3D_CONV_F16_TWO_PLANE, call, f32c, lib, on_device_of
 
 _ONES = {}
 
@@ -66,8 +66,7 @@ def bmm(a, b, alpha=1.0, out=None, relu=False, bias=None, bias_axis="n", accumul
     if bias is not None:
         bias = f32c(bias)
     with on_device_of(a):
-        check(lib().l3d_bmm_f32(ptr(a4), _st(a4), ptr(b4), _st(b4), ptr(o4), _st(o4), nb1, nb2, M, N, K, float(alpha), flags, ptr(bias),
-                                int(parts), ptr(ws), stream_ptr()), "l3d_bmm_f32")
+        call("l3d_bmm_f32", a4, _st(a4), b4, _st(b4), o4, _st(o4), nb1, nb2, M, N, K, float(alpha), flags, bias, int(parts), ws)
     if given:
         # a write through the raw pointer: bump the version autograd and _row_operand's image cache key on
         torch.autograd.graph.increment_version(out)
@@ -126,7 +125,7 @@ class _SoftmaxRows(torch.autograd.Function):
         cols = xc.shape[-1]
         p = torch.empty_like(xc)
         with on_device_of(xc):
-            check(lib().l3d_softmax_rows(ptr(xc), None, xc.numel() // cols, cols, float(scale), ptr(p), stream_ptr()), "l3d_softmax_rows")
+            call("l3d_softmax_rows", xc, None, xc.numel() // cols, cols, float(scale), p)
         ctx.save_for_backward(p)
         ctx.scale = float(scale)
         return p
@@ -138,7 +137,7 @@ class _SoftmaxRows(torch.autograd.Function):
         cols = p.shape[-1]
         dx = torch.empty_like(p)
         with on_device_of(p):
-            check(lib().l3d_softmax_rows(ptr(p), ptr(g), p.numel() // cols, cols, ctx.scale, ptr(dx), stream_ptr()), "l3d_softmax_rows")
+            call("l3d_softmax_rows", p, g, p.numel() // cols, cols, ctx.scale, dx)
         return dx, None
 
 
@@ -174,7 +173,7 @@ def _operand(t, kind):
     """l3d_split_f16_operand of a 2-D fp32 tensor whose rows are contiguous (row stride >= columns)"""
     rows, Cn = t.shape
     img = torch.empty(lib().l3d_f16_image_bytes(2 if kind else 1, rows, Cn), dtype=torch.uint8, device=t.device)
-    check(lib().l3d_split_f16_operand(ptr(t), rows, Cn, t.stride(0), kind, ptr(img), None, stream_ptr()), "l3d_split_f16_operand")
+    call("l3d_split_f16_operand", t, rows, Cn, t.stride(0), kind, img, None)
     return img
 
 
@@ -193,9 +192,9 @@ def _row_operand(x):
 def _f16_product(a_img, rows, K, w_img, N, bias, relu):
     """y [rows, N] = act(A B^T + bias): A = the rows' image (kind 1, [rows][K]), B = an activation-kind image of a [N][K] matrix"""
     y = torch.empty((rows, N), dtype=torch.float32, device=a_img.device)
-    flags = 1 | (4 if bias is not None else 0)
-    check(lib().l3d_pointwise_conv_f16(ptr(w_img), ptr(a_img), None, ptr(bias), 0, 1, K, rows, N, int(bool(relu)), flags,
-                                       ptr(y), None, None, None, None, 0, None, 0, stream_ptr()), "l3d_pointwise_conv_f16[rows]")
+    flags = L3D_CONV_F16_TWO_PLANE | (L3D_CONV_F16_SHIFT_N if bias is not None else 0)
+    call("l3d_pointwise_conv_f16", w_img, a_img, None, bias, 0, 1, K, rows, N, int(bool(relu)), flags, y, None, None, None, None, 0, None, 0,
+         tag="[rows]")
     return y
 
 
@@ -249,7 +248,7 @@ def colsum(g):
     out = torch.empty(Cn, dtype=torch.float32, device=g.device)
     with on_device_of(g):
         ws = torch.empty(lib().l3d_colsum_rows_workspace_bytes(R, Cn), dtype=torch.uint8, device=g.device)
-        check(lib().l3d_colsum_rows(ptr(g), R, Cn, g.stride(0), ptr(ws), ptr(out), stream_ptr()), "l3d_colsum_rows")
+        call("l3d_colsum_rows", g, R, Cn, g.stride(0), ws, out)
     return out
 
 
@@ -274,7 +273,7 @@ class _SquareDistance(torch.autograd.Function):
         M = d.shape[1]
         out = torch.empty((B, N, M), dtype=torch.float32, device=s.device)
         with on_device_of(s):
-            check(lib().l3d_square_distance(ptr(s), ptr(d), B, N, M, Cc, ptr(out), stream_ptr()), "l3d_square_distance")
+            call("l3d_square_distance", s, d, B, N, M, Cc, out)
         ctx.save_for_backward(s, d)
         return out
 
@@ -311,7 +310,7 @@ class _IndexPoints(torch.autograd.Function):
         S = ix.shape[1]
         out = torch.empty((B, S, Cc), dtype=torch.float32, device=p.device)
         with on_device_of(p):
-            check(lib().l3d_index_points(ptr(p), ptr(ix), B, N, Cc, S, ptr(out), stream_ptr()), "l3d_index_points")
+            call("l3d_index_points", p, ix, B, N, Cc, S, out)
         ctx.save_for_backward(ix)
         ctx.n = N
         return out.view(*idx.shape, Cc)

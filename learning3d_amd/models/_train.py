@@ -24,7 +24,7 @@ The running statistics follow torch.nn.BatchNorm (momentum update with the unbia
 import torch
 import torch.distributed as dist
 
-from .._lib import check, f32c, lib, on_device_of, ptr, stream_ptr
+from .._lib import call, f32c, lib, on_device_of
 from . import _fused
 
 
@@ -102,7 +102,7 @@ def sum_clouds(part):
         return tot
     part = part.contiguous()
     tot = torch.empty(part.shape[1:], dtype=torch.float64, device=part.device)
-    check(lib().l3d_sum_clouds_f64(ptr(part), part.shape[0], tot.numel(), ptr(tot), stream_ptr()), "l3d_sum_clouds_f64")
+    call("l3d_sum_clouds_f64", part, part.shape[0], tot.numel(), tot)
     return tot
 
 
@@ -118,7 +118,7 @@ def stats_from_partials(part_global, points_per_cloud):
 def channel_stats(z):
     B, C, P = z.shape
     part = torch.empty((B, C, 2), dtype=torch.float64, device=z.device)
-    check(lib().l3d_channel_stats(ptr(z), B, C, P, ptr(part), stream_ptr()), "l3d_channel_stats")
+    call("l3d_channel_stats", z, B, C, P, part)
     return part
 
 
@@ -136,7 +136,7 @@ def wgrad(dz, x, pc=0):
             pc *= 2
     ws = torch.empty(lib().l3d_wgrad_workspace_bytes(B, Cout, Cin, P, pc) // 4, dtype=torch.float32, device=dz.device)
     dw = torch.empty((Cout, Cin), dtype=torch.float32, device=dz.device)
-    check(lib().l3d_wgrad(ptr(dz), ptr(x), B, Cout, Cin, P, pc, ptr(ws), ptr(dw), stream_ptr()), "l3d_wgrad")
+    call("l3d_wgrad", dz, x, B, Cout, Cin, P, pc, ws, dw)
     return dw
 
 
@@ -172,12 +172,12 @@ class _ConvAffineAct(torch.autograd.Function):
         rstd64, gr64 = torch.empty_like(mean64), torch.empty_like(mean64)
         scale = torch.empty(Cout, dtype=torch.float32, device=dev)
         shift = torch.empty_like(scale)
-        part_ptr, nb, mode, mom, rm, rv = None, 0, 2, 0.0, None, None
+        pg, nb, mode, mom, rm, rv = None, 0, 2, 0.0, None, None
         eps = float(bn.eps) if bn is not None else 0.0
         if bn is not None and batch_stats:
             part = channel_stats(z)
             pg = (gather_cloud_partials(part) if sync else part).contiguous()
-            nb, n, mode, part_ptr = pg.shape[0], float(pg.shape[0]) * float(P), 0, ptr(pg)
+            nb, n, mode = pg.shape[0], float(pg.shape[0]) * float(P), 0
             if bn.track_running_stats and bn.running_mean is not None:
                 if bn.running_mean.dtype != torch.float32 or not bn.running_mean.is_contiguous():
                     raise TypeError("the HIP BatchNorm layer updates fp32 running statistics")
@@ -187,8 +187,7 @@ class _ConvAffineAct(torch.autograd.Function):
                 rm, rv = bn.running_mean, bn.running_var
         elif bn is not None:
             mode, rm, rv = 1, f32c(bn.running_mean.detach()), f32c(bn.running_var.detach())
-        check(lib().l3d_bn_finalize(part_ptr, nb, Cout, n, ptr(bias_f), ptr(gamma_f), ptr(beta_f), eps, mode, float(mom), ptr(rm), ptr(rv),
-                                    ptr(mean64), ptr(rstd64), ptr(gr64), ptr(scale), ptr(shift), stream_ptr()), "l3d_bn_finalize")
+        call("l3d_bn_finalize", pg, nb, Cout, n, bias_f, gamma_f, beta_f, eps, mode, float(mom), rm, rv, mean64, rstd64, gr64, scale, shift)
         if mode == 0 and rm is not None:
             # the kernel updated the running statistics through raw pointers: bump their versions for the caches keyed on them
             # (nothing saved for a backward aliases them: this layer keeps mean64 / rstd64)
@@ -198,7 +197,7 @@ class _ConvAffineAct(torch.autograd.Function):
             y = z
         else:
             y = torch.empty_like(z)
-            check(lib().l3d_bn_act_forward(ptr(z), ptr(scale), ptr(shift), B, Cout, P, int(relu), ptr(y), stream_ptr()), "l3d_bn_act_forward")
+            call("l3d_bn_act_forward", z, scale, shift, B, Cout, P, int(relu), y)
         ctx.relu, ctx.sync, ctx.n, ctx.wshape = relu, sync, n, weight.shape
         ctx.batch_stats, ctx.has_bn = bool(bn is not None and batch_stats), bn is not None
         ctx.pool = int(pool)
@@ -207,7 +206,7 @@ class _ConvAffineAct(torch.autograd.Function):
                 raise ValueError("pooled layer: P must be a multiple of the run length K <= 256 and below 2^22")
             ymax = torch.empty((B, Cout, P // pool), dtype=torch.float32, device=dev)
             pidx = torch.empty(B * Cout * (P // pool), dtype=torch.uint8, device=dev)
-            check(lib().l3d_max_last(ptr(y), pidx.numel(), int(pool), ptr(ymax), ptr(pidx), stream_ptr()), "l3d_max_last")
+            call("l3d_max_last", y, pidx.numel(), int(pool), ymax, pidx)
             ctx.save_for_backward(x, w, z, scale, shift, mean64, rstd64, gr64, pidx)
             return y, ymax
         ctx.save_for_backward(x, w, z, scale, shift, mean64, rstd64, gr64)
@@ -229,9 +228,8 @@ class _ConvAffineAct(torch.autograd.Function):
             dy = torch.zeros_like(z)
         K = ctx.pool if pidx is not None else 0
         part = torch.empty((B, Cout, 2), dtype=torch.float64, device=z.device)
-        check(lib().l3d_bn_backward_stats(ptr(dy), ptr(z), ptr(scale), ptr(shift), ptr(mean64), ptr(rstd64), B, Cout, P,
-                                               int(ctx.relu), ptr(part), ptr(dmax) if pidx is not None else None, ptr(pidx), K,
-                                               stream_ptr()), "l3d_bn_backward_stats")
+        call("l3d_bn_backward_stats", dy, z, scale, shift, mean64, rstd64, B, Cout, P, int(ctx.relu), part,
+             dmax if pidx is not None else None, pidx, K)
         # (sum g, sum g zhat) over this rank's clouds -> parameter gradients; over every rank's -> the batch means: one launch
         pa = gather_cloud_partials(part).contiguous() if (ctx.batch_stats and ctx.sync) else None
         m1 = torch.empty(Cout, dtype=torch.float64, device=z.device)
@@ -239,13 +237,11 @@ class _ConvAffineAct(torch.autograd.Function):
         dbias = torch.empty(Cout, dtype=torch.float32, device=z.device) if ctx.needs_input_grad[2] else None
         dgamma = torch.empty(Cout, dtype=torch.float32, device=z.device) if (ctx.has_bn and ctx.needs_input_grad[3]) else None
         dbeta = torch.empty(Cout, dtype=torch.float32, device=z.device) if (ctx.has_bn and ctx.needs_input_grad[4]) else None
-        check(lib().l3d_bn_backward_finalize(ptr(part), B, ptr(pa), pa.shape[0] if pa is not None else 0, Cout, float(ctx.n),
-                                             int(ctx.batch_stats), ptr(gr64), ptr(m1), ptr(m2), ptr(dbias), ptr(dgamma), ptr(dbeta),
-                                             stream_ptr()), "l3d_bn_backward_finalize")
+        call("l3d_bn_backward_finalize", part, B, pa, pa.shape[0] if pa is not None else 0, Cout, float(ctx.n), int(ctx.batch_stats), gr64,
+             m1, m2, dbias, dgamma, dbeta)
         dz = torch.empty_like(z)
-        check(lib().l3d_bn_act_backward(ptr(dy), ptr(z), ptr(scale), ptr(shift), ptr(mean64), ptr(rstd64), ptr(gr64), ptr(m1), ptr(m2),
-                                             B, Cout, P, int(ctx.relu), ptr(dz), ptr(dmax) if pidx is not None else None, ptr(pidx), K,
-                                             stream_ptr()), "l3d_bn_act_backward")
+        call("l3d_bn_act_backward", dy, z, scale, shift, mean64, rstd64, gr64, m1, m2, B, Cout, P, int(ctx.relu), dz,
+             dmax if pidx is not None else None, pidx, K)
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dx = _fused.pointwise_conv(dz, w.t().contiguous())           # dgrad: [B, Cin, P]
@@ -300,7 +296,7 @@ class _MaxLast(torch.autograd.Function):
         v = torch.empty(x.shape[:-1] + (1,), dtype=torch.float32, device=x.device)
         idx = torch.empty(R, dtype=torch.uint8, device=x.device)
         with on_device_of(x):
-            check(lib().l3d_max_last(ptr(x), R, K, ptr(v), ptr(idx), stream_ptr()), "l3d_max_last")
+            call("l3d_max_last", x, R, K, v, idx)
         ctx.save_for_backward(idx)
         ctx.shape = x.shape
         return v
@@ -311,7 +307,7 @@ class _MaxLast(torch.autograd.Function):
         g = f32c(g)
         gx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
         with on_device_of(g):
-            check(lib().l3d_max_last_backward(ptr(g), ptr(idx), idx.numel(), ctx.shape[-1], ptr(gx), stream_ptr()), "l3d_max_last_backward")
+            call("l3d_max_last_backward", g, idx, idx.numel(), ctx.shape[-1], gx)
         return gx
 
 
@@ -335,7 +331,7 @@ class _LayerNormRef(torch.autograd.Function):
         y = torch.empty_like(xc)
         ac, bc = f32c(a.detach()), f32c(b.detach())
         with on_device_of(xc):
-            check(lib().l3d_layernorm_planes(ptr(xc), ptr(ac), ptr(bc), float(eps), rows, C_, ptr(y), None, stream_ptr()), "l3d_layernorm_planes[values]")
+            call("l3d_layernorm_planes", xc, ac, bc, float(eps), rows, C_, y, None, tag="[values]")
         ctx.save_for_backward(xc, ac)
         ctx.eps = float(eps)
         return y
@@ -351,8 +347,7 @@ class _LayerNormRef(torch.autograd.Function):
         db = torch.empty(C_, dtype=torch.float32, device=xc.device)
         ws = torch.empty(lib().l3d_layernorm_backward_workspace_floats(rows, C_), dtype=torch.float32, device=xc.device)
         with on_device_of(xc):
-            check(lib().l3d_layernorm_ref_backward(ptr(xc), ptr(ac), ptr(g), ctx.eps, rows, C_, ptr(dx), ptr(ws), ptr(da), ptr(db),
-                                                   stream_ptr()), "l3d_layernorm_ref_backward")
+            call("l3d_layernorm_ref_backward", xc, ac, g, ctx.eps, rows, C_, dx, ws, da, db)
         return dx, da, db, None
 
 

@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 from ..utils import pointnet2_utils as pointutils
 from ..utils.model_common_utils import query_ball_point
+from .._lib import call, lib, ptr
 from . import _fused
 
 
@@ -105,7 +106,6 @@ def _factored_first_layer(src_xyz_t, centre_xyz_t, src_feat, centre_feat, idx, o
     if (not FACTOR_FIRST_LAYER or not _fused.can_fuse(module, src_xyz_t, centre_xyz_t, src_feat) or not src_feat.is_cuda
             or idx.dtype != torch.int32 or (centre_feat is not None and not _fused.can_fuse(module, centre_feat))):
         return None
-    from .._lib import check, lib, ptr, stream_ptr
     w, sc, sh = _fused.fold_conv_bn(conv, bn)
     C1, C = w.shape[0], src_feat.shape[1]
     Cc = centre_feat.shape[1] if centre_feat is not None else 0
@@ -137,17 +137,13 @@ def _factored_first_layer(src_xyz_t, centre_xyz_t, src_feat, centre_feat, idx, o
         # |output| <= max|U| + max|V| (or max|shift|) + max_r sum_d |wx_rd| * (max|src coordinate| + max|centre coordinate|): the four
         # data maxima in ONE launch (block maxima; the layer's kernel finishes the reduction and forms the bound itself)
         part = torch.empty(256, dtype=torch.float32, device=U.device)
-        check(lib().l3d_absmax4_partials(ptr(U), U.numel(), ptr(V), V.numel() if V is not None else 0, ptr(sx), sx.numel(),
-                                         ptr(cx), cx.numel(), ptr(part), stream_ptr()), "l3d_absmax4_partials")
+        call("l3d_absmax4_partials", U, U.numel(), V, V.numel() if V is not None else 0, sx, sx.numel(), cx, cx.numel(), part)
         img = torch.empty(lib().l3d_f16_image_bytes(1, B * S * K, C1), dtype=torch.uint8, device=U.device)
-        check(lib().l3d_group_first_layer_planes_auto(ptr(U), ptr(V), ptr(shp), ptr(wx), ptr(sx), ptr(cx), ptr(idx.contiguous()),
-                                                      B, N, S, K, C1, 1, ptr(part), wxr, shmax if V is None else 0.0, ptr(img),
-                                                      ptr(_fused.range_flag(U.device)), stream_ptr()),
-              "l3d_group_first_layer_planes_auto")
+        call("l3d_group_first_layer_planes_auto", U, V, shp, wx, sx, cx, idx.contiguous(), B, N, S, K, C1, 1, part, wxr,
+             shmax if V is None else 0.0, img, ptr(_fused.range_flag(U.device)))
         return img
     out = torch.empty((B, S * K, C1), dtype=torch.float32, device=U.device)
-    check(lib().l3d_group_first_layer(ptr(U), ptr(V), ptr(shp), ptr(wx), ptr(sx), ptr(cx), ptr(idx.contiguous()),
-                                      B, N, S, K, C1, 1, ptr(out), stream_ptr()), "l3d_group_first_layer")
+    call("l3d_group_first_layer", U, V, shp, wx, sx, cx, idx.contiguous(), B, N, S, K, C1, 1, out)
     return out
 
 
@@ -182,7 +178,6 @@ def _grouped_input(src_xyz_t, centre_xyz_t, src_feat, centre_feat, idx, order, m
     if (not _fused.can_fuse(module, src_xyz_t, centre_xyz_t, src_feat) or not src_feat.is_cuda or idx.dtype != torch.int32
             or (centre_feat is not None and not _fused.can_fuse(module, centre_feat))):
         return None
-    from .._lib import check, lib, ptr, stream_ptr
     B, N, _ = src_xyz_t.shape
     S, K = idx.shape[1], idx.shape[2]
     feat = src_feat.float().contiguous()
@@ -190,9 +185,7 @@ def _grouped_input(src_xyz_t, centre_xyz_t, src_feat, centre_feat, idx, order, m
     cen = centre_feat.float().contiguous() if centre_feat is not None else None
     C1 = cen.shape[1] if cen is not None else 0
     out = torch.empty((B, 3 + C + C1, S, K), dtype=torch.float32, device=feat.device)
-    check(lib().l3d_group_concat2(ptr(src_xyz_t.contiguous()), ptr(centre_xyz_t.contiguous()), ptr(feat), ptr(cen),
-                                  ptr(idx.contiguous()), B, N, S, K, C, C1, order, ptr(out), stream_ptr()),
-          "l3d_group_concat2")
+    call("l3d_group_concat2", src_xyz_t.contiguous(), centre_xyz_t.contiguous(), feat, cen, idx.contiguous(), B, N, S, K, C, C1, order, out)
     return out
 
 
@@ -360,7 +353,6 @@ class PointNetFeaturePropogation(nn.Module):
         # reference :268: sum(grouping_operation(feature2, idx) * weight, -1) -- the same three-term weighted
         # sum as pointnet2's three_interpolate, which is one fused kernel (no [B,C,N,3] temporary)
         if _fused.can_fuse(self, feature2, weight) and feature2.is_cuda and (feature1 is None or _fused.can_fuse(self, feature1)):
-            from .._lib import check, lib, ptr, stream_ptr
             f2 = feature2.float().contiguous()
             f1 = feature1.float().contiguous() if feature1 is not None else None
             cin = f2.shape[1] + (f1.shape[1] if f1 is not None else 0)
@@ -369,8 +361,7 @@ class PointNetFeaturePropogation(nn.Module):
                 f1 = torch.cat([f1, f1.new_zeros((B, (-cin) % 16, N))], dim=1)
             c, c1, m = f2.shape[1], (f1.shape[1] if f1 is not None else 0), f2.shape[2]
             feat_new = torch.empty((B, c + c1, N), dtype=torch.float32, device=f2.device)
-            check(lib().l3d_three_interpolate_concat(B, c, m, N, ptr(f2), ptr(idx.contiguous()), ptr(weight.contiguous()),
-                                                     ptr(f1), c1, ptr(feat_new), stream_ptr()), "l3d_three_interpolate_concat")
+            call("l3d_three_interpolate_concat", B, c, m, N, f2, idx.contiguous(), weight.contiguous(), f1, c1, feat_new)
         else:
             interpolated_feat = pointutils.three_interpolate(feature2.contiguous(), idx, weight.contiguous())
             feat_new = torch.cat([interpolated_feat, feature1], 1) if feature1 is not None else interpolated_feat

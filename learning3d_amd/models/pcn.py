@@ -12,6 +12,7 @@ With autograd live, forward is still these kernels (_fused.checkpointed); the ba
 conv / dgrad / wgrad kernels (_train.py) in the reference's op order."""
 import torch
 
+from .._lib import call, f32c
 from . import _fused
 from .pooling import Pooling
 
@@ -154,7 +155,6 @@ class PCN(torch.nn.Module):
         shift = torch.addmm(self.conv5.bias.detach(), gfeat, w5[:, 5:].t())
         if _fused.SPLIT_BF16 and FOLD_FUSED:
             # conv5 -> conv6 -> conv7 (+ centre) as one kernel: the two [B,512,fine] activations never exist
-            from .._lib import check, f32c, lib, ptr, stream_ptr
             w6 = self.conv6.weight.detach().reshape(512, 512)
             f16 = _fused.gemm_arith() == "f16x2"                     # conv6 as f16x2 (3 fp16 products) or bf16x3 (6 bf16)
             w6c = w6.float().contiguous()
@@ -163,10 +163,8 @@ class PCN(torch.nn.Module):
             g_, ce = f32c(x5), f32c(center)
             B, Nf, _ = g_.shape
             out = torch.empty((B, Nf, 3), dtype=torch.float32, device=g_.device)
-            fn, name = (lib().l3d_fold_mlp_f16, "l3d_fold_mlp_f16") if f16 else (lib().l3d_fold_mlp, "l3d_fold_mlp")
-            check(fn(ptr(g_), 5, ptr(f32c(w5[:, :5])), ptr(f32c(shift)), ptr(w6_img),
-                     ptr(f32c(self.conv6.bias.detach())), ptr(f32c(self.conv7.weight.detach().reshape(3, 512))),
-                     ptr(f32c(self.conv7.bias.detach())), ptr(ce), B, Nf, ptr(out), stream_ptr()), name)
+            call("l3d_fold_mlp_f16" if f16 else "l3d_fold_mlp", g_, 5, f32c(w5[:, :5]), f32c(shift), w6_img, f32c(self.conv6.bias.detach()),
+                 f32c(self.conv7.weight.detach().reshape(3, 512)), f32c(self.conv7.bias.detach()), ce, B, Nf, out)
             return out
         h = pc(x5, w5[:, :5], None, shift, relu=True, channel_last=True)
         w, _, b = _fused.fold_conv_bn(self.conv6)

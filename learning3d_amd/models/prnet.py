@@ -18,7 +18,7 @@ import struct
 import torch
 import torch.nn.functional as F
 
-from .._lib import check, lib, ptr, stream_ptr
+from .._lib import call
 from ..utils.model_common_utils import get_graph_feature, knn
 from . import _fused
 
@@ -79,8 +79,7 @@ class DGCNN(torch.nn.Module):
                     pq = _fused.pointwise_conv(h, w, None, t, relu=0)     # [B, 2*cout, N]
                 out = cat[:, lo:lo + cout]
                 with _fused.stage("edge_gather_max"):
-                    check(lib().l3d_edge_gather_max(ptr(pq), ptr(idx), B, cout, N, 20, ACT_LRELU, ptr(out),
-                                                    512 * N, stream_ptr()), "l3d_edge_gather_max")
+                    call("l3d_edge_gather_max", pq, idx, B, cout, N, 20, ACT_LRELU, out, 512 * N)
                 h = out.contiguous() if name != "4" else None
                 lo += cout
             w5, t5, w5_split = self._layer_params("5", self.conv5, self.bn5, stacked=False)

@@ -9,19 +9,18 @@ import math
 
 import torch
 
-from .._lib import check, f32c, lib, ptr, require_gpu, stream_ptr
+from .._lib import call, f32c
 from ..models.dcp import convert2transformation, transform_point_cloud  # noqa: F401  (same functions, one definition)
 
 
 def euler_transform(template, euler_zyx, translation):
     """template [B,N,3] (device), euler_zyx [B,3] = (anglez, angley, anglex) in radians, translation [B,3]
     -> (source [B,N,3], igt [B,4,4]) with the reference's conventions (igt's 3x3 block is the transposed rotation)."""
-    require_gpu(template, euler_zyx, translation)
     t, e, tr = f32c(template), f32c(euler_zyx), f32c(translation)
     B, N, _ = t.shape
     source = torch.empty_like(t)
     igt = torch.empty((B, 4, 4), dtype=torch.float32, device=t.device)
-    check(lib().l3d_euler_transform(ptr(t), ptr(e), ptr(tr), B, N, ptr(source), ptr(igt), stream_ptr()), "l3d_euler_transform")
+    call("l3d_euler_transform", t, e, tr, B, N, source, igt)
     return source, igt
 
 
@@ -89,24 +88,22 @@ class DeepGMRTransform(DCPTransform):
 def twist_transform(template, twist):
     """template [B,N,3] (device), twist [B,6] = (w, v) -> (source [B,N,3], igt [B,4,4] = se3.exp(twist), gt [B,4,4] =
     se3.exp(-twist)): ops/transform_functions.py:133-141 for a whole batch in one launch (l3d_twist_transform)."""
-    require_gpu(template, twist)
     t, x = f32c(template), f32c(twist)
     B, N, _ = t.shape
     source = torch.empty_like(t)
     igt = torch.empty((B, 4, 4), dtype=torch.float32, device=t.device)
     gt = torch.empty((B, 4, 4), dtype=torch.float32, device=t.device)
-    check(lib().l3d_twist_transform(ptr(t), ptr(x), B, N, ptr(source), ptr(igt), ptr(gt), stream_ptr()), "l3d_twist_transform")
+    call("l3d_twist_transform", t, x, B, N, source, igt, gt)
     return source, igt, gt
 
 
 def quat_transform(template, pose7):
     """template [B,N,3], pose7 [B,7] = (quaternion w x y z -- normalised here as create_pose_7d does --, translation)
     -> source = qrot(q, template) + t: PCRNetTransform.__call__ (ops/transform_functions.py:265-269) for a batch."""
-    require_gpu(template, pose7)
     t, p = f32c(template), f32c(pose7)
     B, N, _ = t.shape
     source = torch.empty_like(t)
-    check(lib().l3d_quat_transform(ptr(t), ptr(p), B, N, ptr(source), stream_ptr()), "l3d_quat_transform")
+    call("l3d_quat_transform", t, p, B, N, source)
     return source
 
 

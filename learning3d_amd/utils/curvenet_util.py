@@ -28,7 +28,7 @@ import torch.nn.functional as F
 
 import struct
 
-from .._lib import check, f32c, lib, ptr, require_gpu, stream_ptr
+from .._lib import call, f32c
 from .model_common_utils import farthest_point_sample, index_points, knn, query_ball_point, square_distance  # noqa: F401
 
 FUSED_WALK = True
@@ -40,7 +40,6 @@ _ACT_LRELU = struct.unpack("<i", struct.pack("<f", 0.2))[0]      # activation co
 
 def lpfa_group(xyz, x, idx):
     """xyz [B,3,N], x [B,C,N] or None, idx int64 [B,N,k] -> (geo [B,9,N,k], diff [B,C,N,k] or None)"""
-    require_gpu(xyz, idx)
     B, _, N = xyz.shape
     k = idx.shape[2]
     p = f32c(xyz.transpose(2, 1))
@@ -50,7 +49,7 @@ def lpfa_group(xyz, x, idx):
         xc = f32c(x)
         C = xc.shape[1]
         diff = torch.empty((B, C, N, k), dtype=torch.float32, device=xyz.device)
-    check(lib().l3d_lpfa_group(ptr(p), ptr(xc), ptr(idx.contiguous()), B, N, C, k, ptr(geo), ptr(diff), stream_ptr()), "l3d_lpfa_group")
+    call("l3d_lpfa_group", p, xc, idx.contiguous(), B, N, C, k, geo, diff)
     return geo, diff
 
 
@@ -208,12 +207,11 @@ def gumbel_softmax(logits, dim, temperature=1):
 # ---------------------------------------------------------------------------------------------------------------
 def curve_prepare(x, w_att):
     """x [B,C,N], w_att [C] -> (x sigmoid(w_att . x) as [B,N,C] channel-last, the attention [B,N]): l3d_curve_prepare"""
-    require_gpu(x, w_att)
     x = f32c(x)
     B, C, N = x.shape
     xa = torch.empty((B, N, C), dtype=torch.float32, device=x.device)
     att = torch.empty((B, N), dtype=torch.float32, device=x.device)
-    check(lib().l3d_curve_prepare(ptr(x), ptr(f32c(w_att.reshape(-1))), B, C, N, ptr(xa), ptr(att), stream_ptr()), "l3d_curve_prepare")
+    call("l3d_curve_prepare", x, f32c(w_att.reshape(-1)), B, C, N, xa, att)
     return xa, att
 
 
@@ -221,14 +219,12 @@ def curve_walk(xa, adj, start, params, curve_length):
     """xa [B,N,C] channel-last (already scaled by the attention), adj int64 [B,N,k], start int64 [B,curve_num], params =
     (w_a [2C], a_scale [1], a_shift [1], w_m [2,2C], m_scale [2], m_shift [2]) -> (curves [B,C,curve_num,curve_length], path int32
     [B,curve_num,curve_length]): l3d_curve_walk, one launch"""
-    require_gpu(xa, adj, start, *params)
     xa, adj, start = f32c(xa), adj.to(torch.int64).contiguous(), start.to(torch.int64).contiguous()
     B, N, C = xa.shape
     k, curve_num = adj.shape[2], start.shape[1]
     curves = torch.empty((B, C, curve_num, curve_length), dtype=torch.float32, device=xa.device)
     path = torch.empty((B, curve_num, curve_length), dtype=torch.int32, device=xa.device)
-    check(lib().l3d_curve_walk(ptr(xa), ptr(adj), ptr(start), B, N, C, k, curve_num, curve_length, *[ptr(p) for p in params],
-                               ptr(curves), ptr(path), stream_ptr()), "l3d_curve_walk")
+    call("l3d_curve_walk", xa, adj, start, B, N, C, k, curve_num, curve_length, *params, curves, path)
     return curves, path
 
 

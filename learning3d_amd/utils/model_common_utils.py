@@ -4,11 +4,10 @@ Same function names, argument order, shapes, dtypes and return layouts as the re
 (file:line cited per function); the bodies call the hand-written HIP kernels through the C ABI
 (include/l3d_hip.h) instead of chaining ATen ops that materialise [B,N,N] temporaries.
 """
-import ctypes as C
 
 import torch
 
-from .._lib import L3DError, check, f32c, lib, ptr, require_gpu, stream_ptr
+from .._lib import L3DError, call, f32c, lib, require_gpu
 
 
 def _as_bn3(x_bcn):
@@ -59,14 +58,14 @@ def knn(x, k, add_one_to_k=False):
         if k <= 64 and N <= _FEATKNN_MAX_N:                     # any C (zero-padded to a multiple of 64 in the split pass)
             ws = torch.empty(lib().l3d_knn_feature_workspace_bytes(B, Cc, N), dtype=torch.uint8, device=x.device)
             idx = torch.empty((B, N, k), dtype=torch.int64, device=x.device)
-            check(lib().l3d_knn_feature(ptr(xf), B, Cc, N, k, ptr(ws), ptr(idx), stream_ptr()), "l3d_knn_feature")
+            call("l3d_knn_feature", xf, B, Cc, N, k, ws, idx)
             return idx
         # k > 64 (no caller in the reference asks for it) or a cloud past the kernel's key range: the op sequence itself (:4-8)
         # on the device, a block of queries at a time
         return _knn_feature_rows(xf, k)
     xyz = _as_bn3(x)
     idx = torch.empty((B, N, k), dtype=torch.int64, device=x.device)
-    check(lib().l3d_knn_graph(ptr(xyz), B, N, k, ptr(idx), stream_ptr()), "l3d_knn_graph")
+    call("l3d_knn_graph", xyz, B, N, k, idx)
     return idx
 
 
@@ -89,7 +88,7 @@ def square_distance(src, dst):
         raise RuntimeError(f"square_distance: channel mismatch {Cc} vs {dst.shape[2]}")
     s, d = f32c(src), f32c(dst)
     out = torch.empty((B, N, M), dtype=torch.float32, device=src.device)
-    check(lib().l3d_square_distance(ptr(s), ptr(d), B, N, M, Cc, ptr(out), stream_ptr()), "l3d_square_distance")   # any C
+    call("l3d_square_distance", s, d, B, N, M, Cc, out)   # any C
     return out
 
 
@@ -112,7 +111,7 @@ def index_points(points, idx):
     ix = idx.to(torch.int64).contiguous().view(B, -1)
     S = ix.shape[1]
     out = torch.empty((B, S, Cc), dtype=torch.float32, device=points.device)
-    check(lib().l3d_index_points(ptr(p), ptr(ix), B, N, Cc, S, ptr(out), stream_ptr()), "l3d_index_points")
+    call("l3d_index_points", p, ix, B, N, Cc, S, out)
     return out.view(*idx.shape, Cc)
 
 
@@ -131,8 +130,7 @@ def farthest_point_sample(xyz, npoint, start_with_first_point=False):
     cent = torch.empty((B, npoint), dtype=torch.int64, device=xyz.device)
     from .pointnet2_utils import FPS_REGISTER_N
     temp = torch.empty((B, N), dtype=torch.float32, device=xyz.device) if N > FPS_REGISTER_N else None   # scratch past it
-    check(lib().l3d_farthest_point_sample(ptr(x), B, N, npoint, ptr(start), ptr(temp), ptr(cent), stream_ptr()),
-          "l3d_farthest_point_sample")
+    call("l3d_farthest_point_sample", x, B, N, npoint, start, temp, cent)
     return cent
 
 
@@ -153,7 +151,7 @@ def knn_point(k, pos1, pos2):
     p1, p2 = f32c(pos1), f32c(pos2)
     val = torch.empty((B, M, k), dtype=torch.float32, device=pos1.device)
     idx = torch.empty((B, M, k), dtype=torch.int64, device=pos1.device)
-    check(lib().l3d_knn_point(k, ptr(p1), ptr(p2), B, N, M, ptr(val), ptr(idx), stream_ptr()), "l3d_knn_point")
+    call("l3d_knn_point", k, p1, p2, B, N, M, val, idx)
     return val, idx
 
 
@@ -169,8 +167,7 @@ def query_ball_point(radius, nsample, xyz, new_xyz, get_cnt=False, itself_indice
     idx = torch.empty((B, S, nsample), dtype=torch.int64, device=xyz.device)
     cnt = torch.empty((B, S), dtype=torch.int64, device=xyz.device) if get_cnt else None
     it = itself_indices.to(torch.int64).contiguous() if itself_indices is not None else None
-    check(lib().l3d_query_ball_point(C.c_float(radius), nsample, ptr(x), ptr(q), B, N, S, ptr(it), ptr(idx),
-                                     ptr(cnt), stream_ptr()), "l3d_query_ball_point")
+    call("l3d_query_ball_point", float(radius), nsample, x, q, B, N, S, it, idx, cnt)
     return (idx, cnt) if get_cnt else idx
 
 
@@ -185,7 +182,7 @@ class _GraphFeature(torch.autograd.Function):
         k = idx.shape[2]
         xt = _as_bn3(x) if Cc == 3 else f32c(x.transpose(2, 1))
         out = torch.empty((B, N, k, 2 * Cc), dtype=torch.float32, device=x.device)
-        check(lib().l3d_graph_feature(ptr(xt), ptr(idx), B, N, Cc, k, ptr(out), stream_ptr()), "l3d_graph_feature")
+        call("l3d_graph_feature", xt, idx, B, N, Cc, k, out)
         ctx.save_for_backward(idx)
         ctx.shape = (B, Cc, N)
         return out

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .._lib import check, f32c, lib, ptr, require_gpu, stream_ptr
+from .._lib import call, f32c, require_gpu
 from . import model_common_utils as _m
 
 square_distance = _m.square_distance
@@ -38,8 +38,7 @@ def knn_point(nsample, xyz, new_xyz):
         raise RuntimeError("selected index k out of range")      # what torch.topk raises
     x, q = f32c(xyz), f32c(new_xyz)
     idx = torch.empty((B, S, nsample), dtype=torch.int64, device=xyz.device)
-    check(lib().l3d_knn_point_expanded(nsample, ptr(x), ptr(q), B, N, S, ptr(idx), stream_ptr()),
-          "l3d_knn_point_expanded")
+    call("l3d_knn_point_expanded", nsample, x, q, B, N, S, idx)
     return idx
 
 
@@ -91,7 +90,7 @@ def compute_density(xyz, bandwidth):
         raise NotImplementedError("compute_density: C=3 only")
     x = f32c(xyz)
     out = torch.empty((B, N), dtype=torch.float32, device=xyz.device)
-    check(lib().l3d_gaussian_density(ptr(x), B, N, float(bandwidth), ptr(out), stream_ptr()), "l3d_gaussian_density")
+    call("l3d_gaussian_density", x, B, N, float(bandwidth), out)
     return out
 
 

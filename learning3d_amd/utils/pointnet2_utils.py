@@ -5,14 +5,13 @@ compiles on torch 2.x (THC headers); here the same autograd Functions / Modules 
 Shapes, dtypes (int32 indices), contiguity asserts and argument order follow the reference
 (file:line per class).
 """
-import ctypes as C
 from typing import Tuple
 
 import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from .._lib import check, f32c, lib, on_device_of, ptr, require_gpu, stream_ptr
+from .._lib import call, f32c, lib, on_device_of
 
 
 # Backward of the gather-type ops: True = every target owns its sum and adds its contributions in ascending
@@ -39,8 +38,7 @@ def _scatter_add_det_call(src, idx, weight, T, div, dst):
     B, Cc = src.shape[0], src.shape[1]
     E = idx.numel() // B
     ws = torch.empty(lib().l3d_scatter_add_det_workspace_bytes(B, T, E), dtype=torch.uint8, device=src.device)
-    check(lib().l3d_scatter_add_det(ptr(src), ptr(idx), ptr(weight), B, Cc, T, E, div, ptr(ws), ptr(dst), stream_ptr()),
-          "l3d_scatter_add_det")
+    call("l3d_scatter_add_det", src, idx, weight, B, Cc, T, E, div, ws, dst)
 
 
 def _scatter_add_det(src, idx, weight, T, div):
@@ -78,13 +76,11 @@ class FurthestPointSampling(Function):
     @staticmethod
     def forward(ctx, xyz: torch.Tensor, npoint: int) -> torch.Tensor:
         assert xyz.is_contiguous()
-        require_gpu(xyz)
         B, N, _ = xyz.size()
         output = torch.empty((B, npoint), dtype=torch.int32, device=xyz.device)
         # past FPS_REGISTER_N points the kernel keeps the running distances in temp, like the reference (:25-28)
         temp = torch.empty((B, N), dtype=torch.float32, device=xyz.device) if N > FPS_REGISTER_N else None
-        check(lib().l3d_furthest_point_sampling(B, N, npoint, ptr(xyz), ptr(temp), ptr(output), stream_ptr()),
-              "l3d_furthest_point_sampling")
+        call("l3d_furthest_point_sampling", B, N, npoint, xyz, temp, output)
         ctx.mark_non_differentiable(output)
         return output
 
@@ -103,13 +99,11 @@ class GatherOperation(Function):
     def forward(ctx, features: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         assert features.is_contiguous()
         assert idx.is_contiguous()
-        require_gpu(features, idx)
         B, npoint = idx.size()
         _, Cc, N = features.size()
         idx = idx.int()
         output = torch.empty((B, Cc, npoint), dtype=torch.float32, device=features.device)
-        check(lib().l3d_gather_points(B, Cc, N, npoint, ptr(features), ptr(idx), ptr(output), stream_ptr()),
-              "l3d_gather_points")
+        call("l3d_gather_points", B, Cc, N, npoint, features, idx, output)
         ctx.for_backwards = (idx, Cc, N)
         return output
 
@@ -121,8 +115,7 @@ class GatherOperation(Function):
         if DETERMINISTIC_BACKWARD:
             return _scatter_add_det(g, idx, None, N, 1), None
         grad_features = torch.empty((B, Cc, N), dtype=torch.float32, device=grad_out.device)
-        check(lib().l3d_gather_points_grad(B, Cc, N, npoint, ptr(g), ptr(idx), ptr(grad_features), stream_ptr()),
-              "l3d_gather_points_grad")
+        call("l3d_gather_points_grad", B, Cc, N, npoint, g, idx, grad_features)
         return grad_features, None
 
 
@@ -136,12 +129,11 @@ class KNN(Function):
     def forward(ctx, k: int, unknown: torch.Tensor, known: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         assert unknown.is_contiguous()
         assert known.is_contiguous()
-        require_gpu(unknown, known)
         B, N, _ = unknown.size()
         m = known.size(1)
         dist2 = torch.empty((B, N, k), dtype=torch.float32, device=unknown.device)
         idx = torch.empty((B, N, k), dtype=torch.int32, device=unknown.device)
-        check(lib().l3d_knn(B, N, m, k, ptr(unknown), ptr(known), ptr(dist2), ptr(idx), stream_ptr()), "l3d_knn")
+        call("l3d_knn", B, N, m, k, unknown, known, dist2, idx)
         ctx.mark_non_differentiable(idx)
         return torch.sqrt(dist2), idx
 
@@ -160,13 +152,11 @@ class ThreeNN(Function):
     def forward(ctx, unknown: torch.Tensor, known: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         assert unknown.is_contiguous()
         assert known.is_contiguous()
-        require_gpu(unknown, known)
         B, N, _ = unknown.size()
         m = known.size(1)
         dist2 = torch.empty((B, N, 3), dtype=torch.float32, device=unknown.device)
         idx = torch.empty((B, N, 3), dtype=torch.int32, device=unknown.device)
-        check(lib().l3d_three_nn(B, N, m, ptr(unknown), ptr(known), ptr(dist2), ptr(idx), stream_ptr()),
-              "l3d_three_nn")
+        call("l3d_three_nn", B, N, m, unknown, known, dist2, idx)
         ctx.mark_non_differentiable(idx)
         return torch.sqrt(dist2), idx
 
@@ -186,14 +176,12 @@ class ThreeInterpolate(Function):
         assert features.is_contiguous()
         assert idx.is_contiguous()
         assert weight.is_contiguous()
-        require_gpu(features, idx, weight)
         B, c, m = features.size()
         n = idx.size(1)
         idx = idx.int()
         ctx.three_interpolate_for_backward = (idx, weight, m)
         output = torch.empty((B, c, n), dtype=torch.float32, device=features.device)
-        check(lib().l3d_three_interpolate(B, c, m, n, ptr(features), ptr(idx), ptr(weight), ptr(output),
-                                          stream_ptr()), "l3d_three_interpolate")
+        call("l3d_three_interpolate", B, c, m, n, features, idx, weight, output)
         return output
 
     @staticmethod
@@ -204,8 +192,7 @@ class ThreeInterpolate(Function):
         if DETERMINISTIC_BACKWARD:
             return _scatter_add_det(g, idx, weight, m, 3), None, None
         grad_features = torch.empty((B, c, m), dtype=torch.float32, device=grad_out.device)
-        check(lib().l3d_three_interpolate_grad(B, c, n, m, ptr(g), ptr(idx), ptr(weight), ptr(grad_features),
-                                               stream_ptr()), "l3d_three_interpolate_grad")
+        call("l3d_three_interpolate_grad", B, c, n, m, g, idx, weight, grad_features)
         return grad_features, None, None
 
 
@@ -219,13 +206,11 @@ class GroupingOperation(Function):
     def forward(ctx, features: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         assert features.is_contiguous()
         assert idx.is_contiguous()
-        require_gpu(features, idx)
         idx = idx.int()
         B, nfeatures, nsample = idx.size()
         _, Cc, N = features.size()
         output = torch.empty((B, Cc, nfeatures, nsample), dtype=torch.float32, device=features.device)
-        check(lib().l3d_group_points(B, Cc, N, nfeatures, nsample, ptr(features), ptr(idx), ptr(output),
-                                     stream_ptr()), "l3d_group_points")
+        call("l3d_group_points", B, Cc, N, nfeatures, nsample, features, idx, output)
         ctx.for_backwards = (idx, N)
         return output
 
@@ -237,8 +222,7 @@ class GroupingOperation(Function):
         if DETERMINISTIC_BACKWARD:
             return _scatter_add_det(g.view(B, Cc, npoint * nsample), idx, None, N, 1), None
         grad_features = torch.empty((B, Cc, N), dtype=torch.float32, device=grad_out.device)
-        check(lib().l3d_group_points_grad(B, Cc, N, npoint, nsample, ptr(g), ptr(idx), ptr(grad_features),
-                                          stream_ptr()), "l3d_group_points_grad")
+        call("l3d_group_points_grad", B, Cc, N, npoint, nsample, g, idx, grad_features)
         return grad_features, None
 
 
@@ -255,14 +239,12 @@ class BallQuery(Function):
     def forward(ctx, radius: float, nsample: int, xyz: torch.Tensor, new_xyz: torch.Tensor) -> torch.Tensor:
         assert new_xyz.is_contiguous()
         assert xyz.is_contiguous()
-        require_gpu(xyz, new_xyz)
         B, N, _ = xyz.size()
         npoint = new_xyz.size(1)
         idx = torch.empty((B, npoint, nsample), dtype=torch.int32, device=xyz.device)
         # large clouds: scratch for the cell-list kernels (grouping.hip; the same indices as the scanning kernels)
         ws = torch.empty(B * (16 * N + 16448), dtype=torch.uint8, device=xyz.device) if BALL_QUERY_CELLS and N >= 2048 and nsample <= 64 else None
-        check(lib().l3d_ball_query(B, N, npoint, C.c_float(radius), nsample, ptr(new_xyz), ptr(xyz), ptr(idx), ptr(ws),
-                                   stream_ptr()), "l3d_ball_query")
+        call("l3d_ball_query", B, N, npoint, float(radius), nsample, new_xyz, xyz, idx, ws)
         ctx.mark_non_differentiable(idx)
         return idx
 
@@ -295,10 +277,8 @@ class QueryAndGroup(nn.Module):
             x_, q_ = f32c(xyz), f32c(new_xyz)
             f_ = f32c(features) if features is not None else None
             out = torch.empty((B, (3 if self.use_xyz else 0) + Cf, S, self.nsample), dtype=torch.float32, device=xyz.device)
-            with stage("group_kernel"):                  # the launch alone (bench.py --workload c5: the live HBM-roofline timing)
-                rc = lib().l3d_group_concat(ptr(x_), ptr(q_), ptr(f_), ptr(idx), B, N, S, self.nsample, Cf, int(self.use_xyz),
-                                            ptr(out), stream_ptr())
-            check(rc, "l3d_group_concat")
+            # span: the launch alone (bench.py --workload c5: the live HBM-roofline timing)
+            call("l3d_group_concat", x_, q_, f_, idx, B, N, S, self.nsample, Cf, int(self.use_xyz), out, span=stage("group_kernel"))
             return out
         xyz_trans = xyz.transpose(1, 2).contiguous()
         grouped_xyz = grouping_operation(xyz_trans, idx)                  # (B, 3, npoint, nsample)

@@ -12,17 +12,16 @@ import math
 import torch
 import torch.nn as nn
 
-from .._lib import check, f32c, lib, ptr, require_gpu, stream_ptr
+from .._lib import call, f32c, lib, require_gpu
 
 
 def kabsch(src, src_corr):
     """src, src_corr [B,3,N] -> R [B,3,3], t [B,3]   (utils/svd.py:29-58)."""
-    require_gpu(src, src_corr)
     s, c = f32c(src), f32c(src_corr)
     B, _, N = s.shape
     R = torch.empty((B, 3, 3), dtype=torch.float32, device=s.device)
     t = torch.empty((B, 3), dtype=torch.float32, device=s.device)
-    check(lib().l3d_kabsch(ptr(s), ptr(c), B, N, ptr(R), ptr(t), None, stream_ptr()), "l3d_kabsch")
+    call("l3d_kabsch", s, c, B, N, R, t, None)
     return R, t
 
 
@@ -94,17 +93,15 @@ def soft_correspondence(src_embedding, tgt_embedding, tgt, scale=None):
         scale = 1.0 / math.sqrt(C)
     ws = torch.empty(lib().l3d_soft_correspondence_workspace_floats(B, N, M), dtype=torch.float32, device=q.device)
     out = torch.empty((B, 3, N), dtype=torch.float32, device=q.device)
-    check(lib().l3d_soft_correspondence(ptr(q), ptr(k), ptr(v), B, C, N, M, float(scale), ptr(ws), ptr(out),
-                                        stream_ptr()), "l3d_soft_correspondence")
+    call("l3d_soft_correspondence", q, k, v, B, C, N, M, float(scale), ws, out)
     return out
 
 
 def svd3x3_rotation(H):
     """H [B,3,3] -> R = V U^T with the det < 0 reflection fix   (utils/svd.py:38-49)."""
-    require_gpu(H)
     h = f32c(H)
     R = torch.empty_like(h)
-    check(lib().l3d_svd3x3_rotation(ptr(h), h.shape[0], ptr(R), stream_ptr()), "l3d_svd3x3_rotation")
+    call("l3d_svd3x3_rotation", h, h.shape[0], R)
     return R
 
 

@@ -14,6 +14,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .._lib import call, f32c, lib, on_device_of
+
 
 FLASH_ATTENTION = True      # l3d_attention_forward for d_k in {32, 64, 128}; False: torch matmul + softmax + matmul
 DEFER_LN_VALUES = True      # sublayer norms write only their fp16 plane image; fp32 values on demand (_ln_values)
@@ -49,11 +51,10 @@ def _ln_values(t):
     first; the fast routes never do (they consume the image)."""
     pend = getattr(t, "_l3d_pending", None) if t is not None else None
     if pend is not None:
-        from .._lib import check, lib, ptr, stream_ptr
         xc, ln = pend
         C = xc.size(-1)
-        check(lib().l3d_layernorm_planes(ptr(xc), ptr(ln.a_2.detach().contiguous()), ptr(ln.b_2.detach().contiguous()),
-                                      float(ln.eps), xc.numel() // C, C, ptr(t), None, stream_ptr()), "l3d_layernorm_planes[values]")
+        call("l3d_layernorm_planes", xc, ln.a_2.detach().contiguous(), ln.b_2.detach().contiguous(), float(ln.eps), xc.numel() // C, C,
+             t, None, tag="[values]")
         t._l3d_pending = None
     return t
 
@@ -157,7 +158,6 @@ class LayerNorm(nn.Module):
         C = x.size(-1)
         if (x.is_cuda and x.dtype == torch.float32 and C % 4 == 0 and 1 < C <= 2048
                 and not (torch.is_grad_enabled() and (x.requires_grad or self.a_2.requires_grad))):
-            from .._lib import check, lib, ptr, stream_ptr
             from ..models import _fused
             xc = x.contiguous()
             y = torch.empty_like(xc)
@@ -166,15 +166,14 @@ class LayerNorm(nn.Module):
                 # also emit y as the fp16 plane image of the f16x2 conv kernel: the Linear layers that read this output
                 # (_linear_cf) then need no split pass; the image rides on the tensor object
                 img = torch.empty(lib().l3d_f16_image_bytes(1, rows, C), dtype=torch.uint8, device=xc.device)
-                check(lib().l3d_layernorm_planes(ptr(xc), ptr(self.a_2.detach().contiguous()), ptr(self.b_2.detach().contiguous()),
-                                                 float(self.eps), rows, C, ptr(y) if values else None, ptr(img), stream_ptr()),
-                      "l3d_layernorm_planes")
+                call("l3d_layernorm_planes", xc, self.a_2.detach().contiguous(), self.b_2.detach().contiguous(), float(self.eps), rows, C,
+                     y if values else None, img)
                 y._l3d_planes = img
                 if not values:
                     y._l3d_pending = (xc, self)
                 return y
-            check(lib().l3d_layernorm_planes(ptr(xc), ptr(self.a_2.detach().contiguous()), ptr(self.b_2.detach().contiguous()),
-                                          float(self.eps), rows, C, ptr(y), None, stream_ptr()), "l3d_layernorm_planes[values]")
+            call("l3d_layernorm_planes", xc, self.a_2.detach().contiguous(), self.b_2.detach().contiguous(), float(self.eps), rows, C,
+                 y, None, tag="[values]")
             return y
         if x.is_cuda:
             # autograd live (a training step, or the recompute of a checkpointed forward): HIP forward + one-pass HIP backward
@@ -206,11 +205,9 @@ class SublayerConnection(nn.Module):
                 and not (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad))):
             # the fast sublayers return a [B,N,C] VIEW of channel-first conv output: add through a tiled
             # transpose (l3d_add_transposed) instead of torch's strided elementwise kernel (3x slower)
-            from .._lib import check, lib, ptr, stream_ptr
             out = torch.empty_like(x)
             B, N, C = x.shape
-            check(lib().l3d_add_transposed(ptr(x), ptr(y.transpose(1, 2)), B, N, C, ptr(out), stream_ptr()),
-                  "l3d_add_transposed")
+            call("l3d_add_transposed", x, y.transpose(1, 2), B, N, C, out)
             return out
         return x + y
 
@@ -285,7 +282,6 @@ class MultiHeadedAttention(nn.Module):
                 have_max = all(getattr(z, "_l3d_amax", False) for z in (q, k, v))
             self.attn = None                                   # the [B,h,N,M] map is never formed
             if FLASH_ATTENTION and self.d_k in (32, 64, 128):
-                from .._lib import check, lib, ptr, stream_ptr
                 from ..models import _fused
                 out_lin = self.linears[-1]
                 if (_fused.gemm_arith() == "f16x2" and C_ % 16 == 0
@@ -293,21 +289,16 @@ class MultiHeadedAttention(nn.Module):
                     # both GEMMs as f16x2 (operand scales from the tensors' maxima); the context leaves the kernel as the
                     # fp16 plane image of the f16x2 conv kernel, so the output projection needs no split pass either
                     img = torch.empty(lib().l3d_f16_image_bytes(1, nb * n_q, C_), dtype=torch.uint8, device=q.device)
-                    check(lib().l3d_attention_forward_f16b(ptr(q), ptr(k), ptr(v), nb, self.h, self.d_k, n_q, n_k,
-                                                           q.stride(0), k.stride(0), v.stride(0), 1.0 / math.sqrt(self.d_k),
-                                                           ptr(ws), int(bool(have_max)), None, ptr(img), stream_ptr()),
-                          "l3d_attention_forward_f16b")
+                    call("l3d_attention_forward_f16b", q, k, v, nb, self.h, self.d_k, n_q, n_k, q.stride(0), k.stride(0), v.stride(0),
+                         1.0 / math.sqrt(self.d_k), ws, int(bool(have_max)), None, img)
                     return _linear_cf(out_lin, None, True, planes=(img, nb, n_q)).transpose(1, 2)     # [B,N,C] view
                 ctx = torch.empty((nb, C_, n_q), dtype=torch.float32, device=q.device)
                 if _fused.gemm_arith() == "f16x2":
-                    check(lib().l3d_attention_forward_f16b(ptr(q), ptr(k), ptr(v), nb, self.h, self.d_k, n_q, n_k,
-                                                           q.stride(0), k.stride(0), v.stride(0), 1.0 / math.sqrt(self.d_k),
-                                                           ptr(ws), int(bool(have_max)), ptr(ctx), None, stream_ptr()),
-                          "l3d_attention_forward_f16b")
+                    call("l3d_attention_forward_f16b", q, k, v, nb, self.h, self.d_k, n_q, n_k, q.stride(0), k.stride(0), v.stride(0),
+                         1.0 / math.sqrt(self.d_k), ws, int(bool(have_max)), ctx, None)
                 else:
-                    check(lib().l3d_attention_forward_strided(ptr(q), ptr(k), ptr(v), nb, self.h, self.d_k, n_q, n_k,
-                                                              q.stride(0), k.stride(0), v.stride(0), 1.0 / math.sqrt(self.d_k),
-                                                              ptr(ctx), stream_ptr()), "l3d_attention_forward_strided")
+                    call("l3d_attention_forward_strided", q, k, v, nb, self.h, self.d_k, n_q, n_k, q.stride(0), k.stride(0), v.stride(0),
+                         1.0 / math.sqrt(self.d_k), ctx)
             else:
                 qh, kh, vh = [z.reshape(nb, self.h, self.d_k, z.size(2)) for z in (q, k, v)]
                 p = F.softmax(torch.matmul(qh.transpose(-2, -1), kh) / math.sqrt(self.d_k), dim=-1)   # [B,h,N,M]
@@ -469,18 +460,15 @@ class Transformer(nn.Module):
     @staticmethod
     def _ln_cf(norm, x, values=False, planes=True):
         """LayerNorm over the channels of x [B,C,N] -> (fp32 [B,C,N] or None, plane image or None)"""
-        from .._lib import check, lib, ptr, stream_ptr
         B, C, N = x.shape
         y = torch.empty_like(x) if values else None
         img = torch.empty(lib().l3d_f16_image_bytes(1, B * N, C), dtype=torch.uint8, device=x.device) if planes else None
-        check(lib().l3d_layernorm_planes_cf(ptr(x), ptr(norm.a_2.detach().contiguous()), ptr(norm.b_2.detach().contiguous()),
-                                            float(norm.eps), B, C, N, ptr(y) if values else None, ptr(img) if planes else None,
-                                            int(TWO_PLANE_IMAGES), stream_ptr()), "l3d_layernorm_planes_cf")
+        call("l3d_layernorm_planes_cf", x, norm.a_2.detach().contiguous(), norm.b_2.detach().contiguous(), float(norm.eps), B, C, N,
+             y, img, int(TWO_PLANE_IMAGES))
         return y, img
 
     def _attn_block_cf(self, norm, attn, x, memory):
         """x + attn(norm(x), m, m) with m = norm(x) (self-attention, memory None) or the encoder's output image (memory = (img, N_m))"""
-        from .._lib import check, lib, ptr, stream_ptr
         B, C, N = x.shape
         _, img = self._ln_cf(norm, x)
         ws = _attention_workspace(x.device)
@@ -497,10 +485,8 @@ class Transformer(nn.Module):
             have_max = getattr(q, "_l3d_amax", False) and getattr(kv, "_l3d_amax", False)
         attn.attn = None                                           # the [B,h,N,M] map is never formed
         ctx = torch.empty(lib().l3d_f16_image_bytes(1, B * N, C), dtype=torch.uint8, device=x.device)
-        check(lib().l3d_attention_forward_f16b(ptr(q), ptr(k), ptr(v), B, attn.h, attn.d_k, N, M, q.stride(0), k.stride(0), v.stride(0),
-                                               1.0 / math.sqrt(attn.d_k), ptr(ws), int(bool(have_max)) | (2 if TWO_PLANE_IMAGES else 0), None,
-                                               ptr(ctx), stream_ptr()),
-              "l3d_attention_forward_f16b")
+        call("l3d_attention_forward_f16b", q, k, v, B, attn.h, attn.d_k, N, M, q.stride(0), k.stride(0), v.stride(0),
+             1.0 / math.sqrt(attn.d_k), ws, int(bool(have_max)) | (2 if TWO_PLANE_IMAGES else 0), None, ctx)
         return _linear_cf(attn.linears[-1], None, True, planes=(ctx, B, N), residual=x, two_plane=TWO_PLANE_IMAGES)
 
     def _ffn_block_cf(self, norm, ff, x):
@@ -511,7 +497,6 @@ class Transformer(nn.Module):
 
     def _pass_cf(self, src, tgt):
         """self.model(src^T, tgt^T, None, None)^T for channel-first src, tgt [B,C,N]: the decoder's output [B,C,N_tgt]"""
-        from .._lib import f32c
         enc, dec = self.model.encoder, self.model.decoder
         x = f32c(src)
         for layer in enc.layers:
@@ -527,7 +512,6 @@ class Transformer(nn.Module):
 
     def _forward(self, *input):
         if self._cf_pass_ok(input[0], input[1]):
-            from .._lib import on_device_of
             with on_device_of(input[0], input[1]):
                 tgt_embedding = self._pass_cf(input[0], input[1])
                 src_embedding = self._pass_cf(input[1], input[0])

@@ -2507,3 +2507,16 @@ def test_pointnet_trained_checkpoints_f16x2(golden, tag, use_bn):
             got = net(dev(g["x"])).detach().cpu().numpy()
         np.testing.assert_allclose(got, want, rtol=1e-4, atol=1e-5 * max(1.0, scale), err_msg=f"{tag} {arith}")
     _fused.check_range(sync=True)
+
+
+def test_gather_operation_refuses_other_dtypes():
+    """gather_operation hands its features to a `const float *`: float64 features raise (they used to be read as fp32 and
+    return numbers); on float32 the same shapes equal features[:, :, idx] exactly."""
+    import learning3d_amd.utils.pointnet2_utils as P
+    from learning3d_amd._lib import L3DError
+    feat = dev(rand((1, 2, 8), 5))
+    idx = dev(np.array([[7, 0, 3, 3]], dtype=np.int32))
+    with pytest.raises(L3DError, match="l3d_gather_points.*points.*float32.*float64"):
+        P.gather_operation(feat.double(), idx)
+    got = P.gather_operation(feat, idx)
+    assert torch.equal(got, feat[:, :, idx[0].long()])

@@ -40,6 +40,84 @@ def test_library_exports_every_declared_symbol():
     assert b"invalid" in l.l3d_status_string(-1)
 
 
+def test_prototypes_are_read_from_the_headers():
+    """The ctypes table is derived from include/*.h: one prototype of every kind the parser must get right, held against
+    literal expectations, and a header with a type outside the recognised set raises instead of producing a guess."""
+    import ctypes as C
+    from learning3d_amd import _lib
+    P, I, L, F, D, SZ = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t
+    want = {
+        "l3d_status_string": (C.c_char_p, [I]),
+        "l3d_f16_image_bytes": (SZ, [I, L, I]),
+        "l3d_bmm_f32": (I, [P, P, P, P, P, P, I, I, I, I, I, F, I, P, I, P, P]),
+        "l3d_bn_finalize": (I, [P, I, I, D, P, P, P, D, I, D, P, P, P, P, P, P, P, P]),
+        "l3d_uniform_clouds": (I, [C.c_ulonglong, I, I, F, F, P, P]),
+        "l3d_knn_graph": (I, [P, I, I, I, P, P]),
+        "l3d_gaussian_density": (I, [P, I, I, F, P, P]),
+    }
+    for name, (restype, argtypes) in want.items():
+        assert _lib.PROTOTYPES[name].restype is restype, name
+        assert _lib.SIGNATURES[name] == argtypes, name
+    assert len(_lib.SIGNATURES) == 107
+    par = {name: [(p.ctype, p.name) for p in proto.params] for name, proto in _lib.PROTOTYPES.items()}
+    assert par["l3d_knn_graph"][4] == ("int64_t *", "idx") and par["l3d_knn_graph"][5] == ("l3d_stream_t", "stream")
+    assert par["l3d_bmm_f32"][1] == ("const long *", "a_strides") and par["l3d_bmm_f32"][11] == ("float", "alpha")
+    assert par["l3d_edgeconv_pack"][0] == ("const float *const[]", "w")                 # an array of pointers
+    assert par["l3d_uniform_clouds"][0] == ("unsigned long long", "seed")
+    assert par["l3d_version"] == []
+    # the integer #defines and the l3d_status enumerators come from the same place
+    assert (_lib.L3D_OK, _lib.L3D_ERR_INVALID_ARG, _lib.L3D_ERR_UNSUPPORTED, _lib.L3D_ERR_LAUNCH) == (0, -1, -2, -3)
+    assert (_lib.L3D_CONV_F16_TWO_PLANE, _lib.L3D_CONV_F16_OUT_UNSCALED, _lib.L3D_CONV_F16_SHIFT_N, _lib.L3D_KNN_MAX_K) == (1, 2, 4, 200)
+    # the array form of a parameter, and what the parser must refuse
+    protos, consts = _lib.parse_header("/* c */\n#define L3D_X 0x10\nint l3d_f(const long st[4], unsigned n,\n          l3d_stream_t stream);\n")
+    assert consts == {"L3D_X": 16} and protos["l3d_f"].restype is I
+    assert [(p.ctype, p.name) for p in protos["l3d_f"].params] == [("const long[]", "st"), ("unsigned", "n"), ("l3d_stream_t", "stream")]
+    for bad in ("int l3d_f(const __half *x, int n);", "int l3d_f(struct s v);", "half l3d_f(void);", "int l3d_f(float *);",
+                "int l3d_f(int (*cb)(int));"):
+        with pytest.raises(_lib.L3DError, match=r"t\.h:3"):
+            _lib.parse_header("\n\n" + bad + "\n", "t.h")
+
+
+def test_call_checks_tensor_dtypes_before_devices():
+    """_lib.call holds a tensor against the element type of the parameter it is passed for, before the device rule -- so on CPU
+    tensors the dtype errors, and then the no-CPU-fallback error, are reached without a launch."""
+    import ctypes as C
+    from learning3d_amd import _lib
+    f32, f64 = torch.zeros(1, 2, 8), torch.zeros(1, 2, 8, dtype=torch.float64)
+    i32, i64 = torch.zeros(1, 4, dtype=torch.int32), torch.zeros(1, 4, dtype=torch.int64)
+    out = torch.zeros(1, 2, 4)
+    with pytest.raises(_lib.L3DError, match=r"l3d_gather_points.*`const float \*points`.*torch\.float32.*torch\.float64"):
+        _lib.call("l3d_gather_points", 1, 2, 8, 4, f64, i32, out)
+    with pytest.raises(_lib.L3DError, match=r"l3d_gather_points.*`const int32_t \*idx`.*torch\.int32.*torch\.int64"):
+        _lib.call("l3d_gather_points", 1, 2, 8, 4, f32, i64, out)
+    with pytest.raises(_lib.L3DError, match=r"l3d_gather_points.*`const float \*points`.*torch\.float16"):
+        _lib.call("l3d_gather_points", 1, 2, 8, 4, f32.half(), i32, out)
+    with pytest.raises(_lib.L3DError, match="no CPU fallback"):
+        _lib.call("l3d_gather_points", 1, 2, 8, 4, f32, i32, out)
+    # None for an optional pointer and a ctypes array for `const long *` get as far as the device rule
+    st = (C.c_long * 4)(0, 0, 8, 1)
+    with pytest.raises(_lib.L3DError, match="no CPU fallback"):
+        _lib.call("l3d_bmm_f32", f32, st, f32, st, out, st, 1, 1, 2, 2, 8, 1.0, 0, None, 1, None)
+    with pytest.raises(_lib.L3DError, match="no CPU fallback"):
+        _lib.call("l3d_furthest_point_sampling", 1, 8, 4, torch.zeros(1, 8, 3), None, i32)
+    # void * takes any dtype; a tensor for a scalar, a wrong argument count and an unknown name are errors
+    with pytest.raises(_lib.L3DError, match="no CPU fallback"):
+        _lib.call("l3d_split_rows", f32, 2, 8, torch.zeros(64, dtype=torch.uint8))
+    with pytest.raises(_lib.L3DError, match=r"l3d_gather_points.*`int npoints`.*by value"):
+        _lib.call("l3d_gather_points", 1, 2, 8, i32, f32, i32, out)
+    with pytest.raises(_lib.L3DError, match=r"l3d_gather_points.*8 arguments"):
+        _lib.call("l3d_gather_points", 1, 2, 8, 4, f32, i32)
+    with pytest.raises(KeyError):
+        _lib.call("l3d_no_such_entry_point")
+    log, _lib.LAUNCH_LOG = _lib.LAUNCH_LOG, []
+    try:
+        with pytest.raises(_lib.L3DError, match=r"l3d_knn_graph\[probe\]: .*invalid"):
+            _lib.call("l3d_knn_graph", None, 1, 8, 4, None, None, tag="[probe]")       # stream given; NULL pointers: refused before any launch
+        assert _lib.LAUNCH_LOG == ["l3d_knn_graph[probe]"]
+    finally:
+        _lib.LAUNCH_LOG = log
+
+
 def test_argument_validation_without_gpu():
     from learning3d_amd import _lib
     l = _lib.lib()
