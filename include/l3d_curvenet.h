@@ -28,7 +28,8 @@ int l3d_curve_prepare(const float *x, const float *w_att, int B, int C, int N, f
  * x [B,N,C] channel-last (already scaled by the attention), adj int64 [B,N,k], start int64 [B,curve_num] (entries outside
  * [0,N) are clamped into it), w_a [2C], a_scale / a_shift [1], w_m [2,2C], m_scale / m_shift [2].
  * curves [B,C,curve_num,curve_length]; path int32 [B,curve_num,curve_length]: the point picked at each step.
- * C % 16 == 0, C <= 128, k <= 64, curve_num <= N, curve_num (2 C + 3) <= 16384 (a cloud's curves share one workgroup's LDS). */
+ * C % 16 == 0, C <= 128, k <= 64, curve_num <= N, curve_num (2 C + 3) <= 16384 (a cloud's curves share one workgroup's LDS),
+ * x 16-byte aligned (its rows are read 16 bytes at a time); else L3D_ERR_UNSUPPORTED. */
 int l3d_curve_walk(const float *x, const int64_t *adj, const int64_t *start, int B, int N, int C, int k, int curve_num,
                    int curve_length, const float *w_a, const float *a_scale, const float *a_shift, const float *w_m,
                    const float *m_scale, const float *m_shift, float *curves, int32_t *path, l3d_stream_t stream);

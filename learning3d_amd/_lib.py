@@ -197,6 +197,14 @@ def f32c(t):
     return t.contiguous()
 
 
+def f32a(t):
+    """f32c(t) on a 16-byte boundary: a contiguous slice of a larger buffer (x[1:], a chunk of a flat tensor) is a legal input whose
+    data pointer is only 4-byte aligned, and the entry points that read their operand 16 bytes at a time without a scalar route
+    refuse it (L3D_ERR_UNSUPPORTED).  Their wrappers pass the operand through here: a copy when it is misaligned, t itself else."""
+    t = f32c(t)
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def _bad_argument(name, i, a, want):
     p = PROTOTYPES[name].params[i]
     decl = p.ctype + ("" if p.ctype.endswith("*") else " ") + p.name

@@ -607,7 +607,7 @@ __global__ __launch_bounds__(1024) void sqrt_sum_kernel(const float *__restrict_
     const float *d = which == 0 ? d1 : d2;
     const size_t n = which == 0 ? n1 : n2;
     double acc = 0.0;
-    const size_t n4 = n >> 2;                          // 16-byte loads, 4 independent sqrt per trip
+    const size_t n4 = (((size_t)d) & 15) == 0 ? n >> 2 : 0;      // 16-byte loads, 4 independent sqrt per trip (an unaligned d: the scalar loop below takes it all)
     for (size_t i = threadIdx.x; i < n4; i += blockDim.x) {
         const float4 v = ((const float4 *)d)[i];
         acc += ((double)sqrtf(v.x) + (double)sqrtf(v.y)) + ((double)sqrtf(v.z) + (double)sqrtf(v.w));
@@ -646,7 +646,8 @@ __global__ __launch_bounds__(256) void chamfer_loss_local_mb_kernel(const float 
     __shared__ double part[2][4];
     __shared__ bool last;
     double acc1 = 0.0, acc2 = 0.0;
-    const size_t a4 = n1 >> 2, b4 = n2 >> 2, m4 = a4 > b4 ? a4 : b4;
+    // 16-byte loads from a 16-byte aligned tensor only: an unaligned one goes through workgroup 0's scalar loop below
+    const size_t a4 = (((size_t)d1) & 15) == 0 ? n1 >> 2 : 0, b4 = (((size_t)d2) & 15) == 0 ? n2 >> 2 : 0, m4 = a4 > b4 ? a4 : b4;
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < m4; i += stride) {
         if (i < a4) {

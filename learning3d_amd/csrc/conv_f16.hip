@@ -257,7 +257,7 @@ __global__ __launch_bounds__(256) void cf_split_x_cl_kernel(const float *__restr
             if (row < R && o * 8 < C) {
                 if (rinv) upr = 1.0f / rinv[row];
                 const float *p = src + (size_t)row * sstride + o * 8;
-                if (o * 8 + 8 <= C && (C & 3) == 0 && (sstride & 3) == 0) {
+                if (o * 8 + 8 <= C && (C & 3) == 0 && (sstride & 3) == 0 && (((size_t)src) & 15) == 0) {     // 16-byte addressable rows
                     const f32x4 a = *(const f32x4 *)p, b = *(const f32x4 *)(p + 4);
                     v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
                 } else {

@@ -510,7 +510,7 @@ static int launch_conv_split(const void *x, int x_mode, const void *w_split, con
                              int shift_bstride, int B, int Cin, int Cout, int N, int relu, int pool, float *y,
                              hipStream_t st)
 {
-    if (Cout % CS_TM || N % CD_TN || Cin % CS_TK || B > 65535 || (((size_t)x) & 15)) return L3D_ERR_UNSUPPORTED;
+    if (Cout % CS_TM || N % CD_TN || Cin % CS_TK || B > 65535 || ((((size_t)x) | ((size_t)w_split)) & 15)) return L3D_ERR_UNSUPPORTED;
     if (pool && N % CS_TN) return L3D_ERR_UNSUPPORTED;          // the pooled epilogue lives in the 256x256 kernel only
     // Both shapes run conv5 in ~170 us (tools/probe_conv_split.hip ablations: the 256x128 shape moves
     // 1.6x the bytes per FLOP through the CU's vector-memory path, which cancels what its two

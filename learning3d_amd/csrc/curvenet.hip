@@ -191,7 +191,8 @@ extern "C" int l3d_curve_walk(const float *x, const int64_t *adj, const int64_t 
 {
     L3D_REQUIRE(x && adj && start && w_a && a_scale && a_shift && w_m && m_scale && m_shift && curves && path);
     L3D_REQUIRE(B > 0 && N > 0 && C > 0 && k > 0 && curve_num > 0 && curve_length > 0);
-    if (C % 16 || C > CW_MAXC || k > 64 || curve_num > N || B > (1 << 24)) return L3D_ERR_UNSUPPORTED;
+    // the candidates' rows of x are read 16 bytes at a time (C % 16 == 0: every row starts where x does, modulo 16)
+    if (C % 16 || C > CW_MAXC || k > 64 || curve_num > N || B > (1 << 24) || (((size_t)x) & 15)) return L3D_ERR_UNSUPPORTED;
     const size_t lds = (size_t)curve_num * (2 * C + 3) * sizeof(float);
     if (lds > CW_MAX_LDS) return L3D_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(curve_walk_kernel, dim3(B), dim3(CW_WAVES * 64), lds, (hipStream_t)stream, x, adj, start, N, C, k, curve_num,

@@ -346,7 +346,7 @@ extern "C" int l3d_edgeconv_forward_split(const float *xyz, const int64_t *idx, 
                                           const float *packed, float *pooled, l3d_stream_t stream)
 {
     L3D_REQUIRE(xyz && idx && packed && pooled && B > 0 && N > 0 && k > 0);
-    if (k > 20 || B > 65535 || (((size_t)packed) & 15)) return L3D_ERR_UNSUPPORTED;
+    if (k > 20 || B > 65535 || ((((size_t)packed) | ((size_t)pooled)) & 15)) return L3D_ERR_UNSUPPORTED;
     dim3 grid(l3d_divup(N, 16), B), block(256);
     hipStream_t st = (hipStream_t)stream;
     if (k <= 16) hipLaunchKernelGGL(edgeconv_split_kernel<4>, grid, block, 0, st, xyz, idx, N, k, packed, pooled);

@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void emd_match_kernel(int n, int m, const floa
     __syncthreads();
     float cost = 0.f;
     float *mrow = match + ((size_t)b * m + l0) * n;
-    const bool pair_store = v1 && (n & 1) == 0;            // 8-byte aligned when n is even (k0 is)
+    const bool pair_store = v1 && (n & 1) == 0 && (((size_t)match) & 7) == 0;      // 8-byte aligned when match is and n is even (k0 is)
     for (int li = 0; li < lt; li++) {
         const float4 c = pl[li];
         const f32x2 dx = (f32x2){c.x, c.x} - X2, dy = (f32x2){c.y, c.y} - Y2, dz = (f32x2){c.z, c.z} - Z2;

@@ -197,7 +197,7 @@ extern "C" int l3d_fold_mlp(const float *g, int CG, const float *w5g, const floa
                             float *out, l3d_stream_t stream)
 {
     L3D_REQUIRE(g && w5g && s5 && w6_split && b6 && w7 && b7 && centre && out && B > 0 && N > 0);
-    if (B > 65535 || CG != 5) return L3D_ERR_UNSUPPORTED;
+    if (B > 65535 || CG != 5 || (((size_t)w6_split) & 15)) return L3D_ERR_UNSUPPORTED;
     dim3 grid(l3d_divup(N, 256), B), block(512);
     hipLaunchKernelGGL(fold_mlp_kernel<5>, grid, block, FM_LDS, (hipStream_t)stream, g, w5g, s5, (const uint4 *)w6_split, b6,
                        w7, b7, centre, N, out);

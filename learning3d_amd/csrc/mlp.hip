@@ -511,7 +511,8 @@ __global__ __launch_bounds__(256, 2) void pointwise_conv_kernel(
     //   B (channel-first): thread -> (k = tid/16, 8 consecutive n at (tid&15)*8)
     //   B (channel-last) : thread -> (n = tid/2,  8 consecutive k at (tid&1)*8)
     float ra[8], rb[8];
-    const bool cin_vec = (Cin & 3) == 0, n_vec = (N & 3) == 0;
+    // 16-byte loads need the row length a multiple of 4 AND the tensor 16-byte aligned (a contiguous slice of a caller's buffer need not be)
+    const bool w_vec = (Cin & 3) == 0 && (((size_t)w) & 15) == 0, x_vec = ((XCL ? Cin : N) & 3) == 0 && (((size_t)x) & 15) == 0;
     auto load8 = [](float (&r)[8], const float *src, int pos, int limit, bool row_ok, bool vec) {
         if (FULL || (row_ok && vec && pos + 8 <= limit)) {
             const float4 v0 = *(const float4 *)(src + pos), v1 = *(const float4 *)(src + pos + 4);
@@ -531,16 +532,16 @@ __global__ __launch_bounds__(256, 2) void pointwise_conv_kernel(
         {
             const int co = co0 + (tid >> 1);
             const bool rok = co < Cout;
-            load8(ra, w + (size_t)(rok ? co : 0) * Cin, k0 + (tid & 1) * 8, Cin, rok, cin_vec);
+            load8(ra, w + (size_t)(rok ? co : 0) * Cin, k0 + (tid & 1) * 8, Cin, rok, w_vec);
         }
         if (XCL) {
             const int n = n0 + (tid >> 1);
             const bool nok = n < N;
-            load8(rb, xb + (size_t)(nok ? n : 0) * Cin, k0 + (tid & 1) * 8, Cin, nok, cin_vec);
+            load8(rb, xb + (size_t)(nok ? n : 0) * Cin, k0 + (tid & 1) * 8, Cin, nok, x_vec);
         } else {
             const int kk = k0 + (tid >> 4);
             const bool kok = kk < Cin;
-            load8(rb, xb + (size_t)(kok ? kk : 0) * N, n0 + (tid & 15) * 8, N, kok, n_vec);
+            load8(rb, xb + (size_t)(kok ? kk : 0) * N, n0 + (tid & 15) * 8, N, kok, x_vec);
         }
     };
     auto store_chunk = [&]() {

@@ -280,6 +280,7 @@ extern "C" int l3d_sum_clouds_f64(const double *part, int B, long M, double *tot
 // backward a zero fill plus an index scatter; here a thread takes a row, the arg-max is the FIRST maximum (torch's rule) in one
 // byte, and the backward writes the dense gradient in one pass.
 // ---------------------------------------------------------------------------------------------
+template <bool VEC>
 __global__ __launch_bounds__(256) void max_last_kernel(const float *__restrict__ x, long R, int K, float *__restrict__ v,
                                                        unsigned char *__restrict__ idx)
 {
@@ -289,7 +290,7 @@ __global__ __launch_bounds__(256) void max_last_kernel(const float *__restrict__
     float best = row[0];
     int bi = 0;
     bool nan = best != best;
-    if ((K & 3) == 0) {
+    if (VEC) {                                       // K % 4 == 0 and x 16-byte aligned: every row starts on a 16-byte boundary
         for (int k = 0; k < K; k += 4) {
             const float4 q = *(const float4 *)(row + k);
             const float e[4] = {q.x, q.y, q.z, q.w};
@@ -314,7 +315,7 @@ __global__ __launch_bounds__(256) void max_last_kernel(const float *__restrict__
     idx[r] = (unsigned char)bi;
 }
 
-// K % 4 == 0: a thread per float4 of gx (consecutive lanes write consecutive 16 bytes: whole cache lines per wave store; a thread
+// K % 4 == 0 and gx 16-byte aligned: a thread per float4 of gx (consecutive lanes write consecutive 16 bytes: whole cache lines per wave store; a thread
 // per 80-byte row wrote 40 partial lines per store instruction and ran at 1 TB/s); the row's g and idx come through the cache
 template <bool VEC>
 __global__ __launch_bounds__(256) void max_last_backward_kernel(const float *__restrict__ g, const unsigned char *__restrict__ idx,
@@ -337,12 +338,16 @@ __global__ __launch_bounds__(256) void max_last_backward_kernel(const float *__r
     }
 }
 
-// v [R] = max_k x [R][K], idx [R] = the first k that attains it (one byte: K <= 256); x 16-byte aligned
+// v [R] = max_k x [R][K], idx [R] = the first k that attains it (one byte: K <= 256); 16-byte loads when K % 4 == 0 and x is
+// 16-byte aligned, the scalar loop (the same comparisons in the same order) otherwise
 extern "C" int l3d_max_last(const float *x, long R, int K, float *v, unsigned char *idx, l3d_stream_t stream)
 {
     L3D_REQUIRE(x && v && idx && R > 0 && K > 0);
-    if (K > 256 || (((size_t)x) & 15) || l3d_divup(R, 256) > 0x7fffffffL) return L3D_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(max_last_kernel, dim3((unsigned)l3d_divup(R, 256)), dim3(256), 0, (hipStream_t)stream, x, R, K, v, idx);
+    if (K > 256 || l3d_divup(R, 256) > 0x7fffffffL) return L3D_ERR_UNSUPPORTED;
+    if (K % 4 == 0 && (((size_t)x) & 15) == 0)
+        hipLaunchKernelGGL(max_last_kernel<true>, dim3((unsigned)l3d_divup(R, 256)), dim3(256), 0, (hipStream_t)stream, x, R, K, v, idx);
+    else
+        hipLaunchKernelGGL(max_last_kernel<false>, dim3((unsigned)l3d_divup(R, 256)), dim3(256), 0, (hipStream_t)stream, x, R, K, v, idx);
     return l3d_check_launch();
 }
 
@@ -350,8 +355,8 @@ extern "C" int l3d_max_last(const float *x, long R, int K, float *v, unsigned ch
 extern "C" int l3d_max_last_backward(const float *g, const unsigned char *idx, long R, int K, float *gx, l3d_stream_t stream)
 {
     L3D_REQUIRE(g && idx && gx && R > 0 && K > 0);
-    if (K > 256 || (((size_t)gx) & 15) || l3d_divup(R * (long)((K + 3) / 4), 256) > 0x7fffffffL) return L3D_ERR_UNSUPPORTED;
-    if (K % 4 == 0)
+    if (K > 256 || l3d_divup(R * (long)((K + 3) / 4), 256) > 0x7fffffffL) return L3D_ERR_UNSUPPORTED;
+    if (K % 4 == 0 && (((size_t)gx) & 15) == 0)
         hipLaunchKernelGGL(max_last_backward_kernel<true>, dim3((unsigned)l3d_divup(R * (K / 4), 256)), dim3(256), 0, (hipStream_t)stream, g,
                            idx, R, K, gx);
     else

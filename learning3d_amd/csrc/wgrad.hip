@@ -18,7 +18,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define WG_LD 66       // LDS row pitch (floats): the 8-wide k runs of the four lanes sharing a row land 16 banks apart
 
 __global__ __launch_bounds__(256) void wgrad_partial_kernel(const float *__restrict__ dz, const float *__restrict__ x, int Cout,
-                                                            int Cin, long P, int PC, int nchunk, float *__restrict__ part)
+                                                            int Cin, long P, int PC, int nchunk, int vec, float *__restrict__ part)
 {
     __shared__ float As[WG_K][WG_LD], Bs[WG_K][WG_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -28,8 +28,6 @@ __global__ __launch_bounds__(256) void wgrad_partial_kernel(const float *__restr
     const long p_begin = (long)chunk * PC;
     const long p_end = (p_begin + PC < P) ? p_begin + PC : P;
     const float *dzb = dz + (size_t)b * Cout * P, *xb = x + (size_t)b * Cin * P;
-    const bool vec = (P % 4) == 0;
-
     const int row = tid >> 2, kb = (tid & 3) * 8;
     float ra[8], rb[8];
     auto load8 = [&](float (&r)[8], const float *base, int rr, int rows, long p) {
@@ -132,8 +130,11 @@ extern "C" int l3d_wgrad(const float *dz, const float *x, int B, int Cout, int C
     const long nchunk = (P + pc - 1) / pc;
     const long pieces = (long)B * nchunk;
     L3D_REQUIRE(pieces <= 65535 && l3d_divup(Cin, WG_T) <= 65535);
+    // 16-byte loads along P: every row of dz and x then starts on a 16-byte boundary (the chunks start at multiples of 32 points)
+    const int vec = P % 4 == 0 && ((((size_t)dz) | ((size_t)x)) & 15) == 0;
     dim3 grid(l3d_divup(Cout, WG_T), l3d_divup(Cin, WG_T), (unsigned)pieces);
-    hipLaunchKernelGGL(wgrad_partial_kernel, grid, dim3(256), 0, (hipStream_t)stream, dz, x, Cout, Cin, P, pc, (int)nchunk, workspace);
+    hipLaunchKernelGGL(wgrad_partial_kernel, grid, dim3(256), 0, (hipStream_t)stream, dz, x, Cout, Cin, P, pc, (int)nchunk, vec,
+                       workspace);
     int rc = l3d_check_launch();
     if (rc != L3D_OK) return rc;
     const long elems = (long)Cout * Cin;

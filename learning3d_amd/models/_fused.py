@@ -16,7 +16,7 @@ import threading
 
 import torch
 
-from .._lib import L3D_CONV_F16_OUT_UNSCALED, L3D_CONV_F16_TWO_PLANE, call, f32c, lib, ptr, require_gpu
+from .._lib import L3D_CONV_F16_OUT_UNSCALED, L3D_CONV_F16_TWO_PLANE, call, f32a, f32c, lib, ptr, require_gpu
 
 
 class _NullSpan:
@@ -466,8 +466,8 @@ def pointwise_conv_maxpool(x, w, scale, shift, relu, pool, w_split=None, channel
     if split_eligible(Cin, Cout, N) and N % 256 == 0:
         if w_split is None:
             w_split = split_rows(w)
-        call("l3d_pointwise_conv_split", x, int(channel_last), w_split, scale, shift, bstride, B, Cin, Cout, N, int(relu), pool, y,
-             tag="[maxpool]")
+        call("l3d_pointwise_conv_split", f32a(x), int(channel_last), w_split, scale, shift, bstride, B, Cin, Cout, N, int(relu), pool, y,
+             tag="[maxpool]")                               # (f32a: the bf16x3 kernel reads x 16 bytes at a time and refuses a misaligned one)
         return y
     call("l3d_pointwise_conv", x, int(channel_last), w, scale, shift, bstride, B, Cin, Cout, N, int(relu), pool, y, tag="[maxpool]")
     return y
@@ -510,7 +510,8 @@ def pointwise_conv(x, w, scale=None, shift=None, relu=False, channel_last=False,
     if use_split:
         if w_split is None:
             w_split = split_rows(w)
-        call("l3d_pointwise_conv_split", x, int(channel_last), w_split, scale, shift, bstride, B, Cin, Cout, N, int(relu), 0, y)
+        # (f32a: the bf16x3 kernel reads x 16 bytes at a time and refuses a misaligned one: a contiguous slice of a larger buffer is copied)
+        call("l3d_pointwise_conv_split", f32a(x), int(channel_last), w_split, scale, shift, bstride, B, Cin, Cout, N, int(relu), 0, y)
         return y
     call("l3d_pointwise_conv", x, int(channel_last), w, scale, shift, bstride, B, Cin, Cout, N, int(relu), 0, y)
     return y
@@ -523,6 +524,7 @@ def linear_rows(x, lin, relu=False):
     x = f32c(x)
     R, Cin = x.shape
     if Cin % 256 == 0:
+        x, w = f32a(x), f32a(w)                                          # l3d_linear_rows refuses a misaligned x / w
         y = torch.empty((R, w.shape[0]), dtype=torch.float32, device=x.device)
         call("l3d_linear_rows", x, w, b, R, Cin, w.shape[0], int(relu), y)
         return y

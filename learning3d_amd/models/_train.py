@@ -24,7 +24,7 @@ The running statistics follow torch.nn.BatchNorm (momentum update with the unbia
 import torch
 import torch.distributed as dist
 
-from .._lib import call, f32c, lib, on_device_of
+from .._lib import call, f32a, f32c, lib, on_device_of
 from . import _fused
 
 
@@ -325,11 +325,11 @@ class _LayerNormRef(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, a, b, eps):
-        xc = f32c(x)
-        C_ = xc.shape[-1]
+        xc = f32a(x)                                                     # both kernels read whole rows 16 bytes at a time and refuse
+        C_ = xc.shape[-1]                                                # a misaligned x / a / b / g: those are copied first (f32a)
         rows = xc.numel() // C_
         y = torch.empty_like(xc)
-        ac, bc = f32c(a.detach()), f32c(b.detach())
+        ac, bc = f32a(a.detach()), f32a(b.detach())
         with on_device_of(xc):
             call("l3d_layernorm_planes", xc, ac, bc, float(eps), rows, C_, y, None, tag="[values]")
         ctx.save_for_backward(xc, ac)
@@ -339,7 +339,7 @@ class _LayerNormRef(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         xc, ac = ctx.saved_tensors
-        g = f32c(g)
+        g = f32a(g)
         C_ = xc.shape[-1]
         rows = xc.numel() // C_
         dx = torch.empty_like(xc)

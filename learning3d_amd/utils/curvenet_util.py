@@ -28,7 +28,7 @@ import torch.nn.functional as F
 
 import struct
 
-from .._lib import call, f32c
+from .._lib import call, f32a, f32c
 from .model_common_utils import farthest_point_sample, index_points, knn, query_ball_point, square_distance  # noqa: F401
 
 FUSED_WALK = True
@@ -219,7 +219,8 @@ def curve_walk(xa, adj, start, params, curve_length):
     """xa [B,N,C] channel-last (already scaled by the attention), adj int64 [B,N,k], start int64 [B,curve_num], params =
     (w_a [2C], a_scale [1], a_shift [1], w_m [2,2C], m_scale [2], m_shift [2]) -> (curves [B,C,curve_num,curve_length], path int32
     [B,curve_num,curve_length]): l3d_curve_walk, one launch"""
-    xa, adj, start = f32c(xa), adj.to(torch.int64).contiguous(), start.to(torch.int64).contiguous()
+    # (f32a: the walk reads the candidates' rows 16 bytes at a time and refuses a misaligned xa -- a contiguous slice is copied)
+    xa, adj, start = f32a(xa), adj.to(torch.int64).contiguous(), start.to(torch.int64).contiguous()
     B, N, C = xa.shape
     k, curve_num = adj.shape[2], start.shape[1]
     curves = torch.empty((B, C, curve_num, curve_length), dtype=torch.float32, device=xa.device)

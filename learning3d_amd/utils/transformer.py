@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .._lib import call, f32c, lib, on_device_of
+from .._lib import call, f32a, f32c, lib, on_device_of
 
 
 FLASH_ATTENTION = True      # l3d_attention_forward for d_k in {32, 64, 128}; False: torch matmul + softmax + matmul
@@ -53,7 +53,7 @@ def _ln_values(t):
     if pend is not None:
         xc, ln = pend
         C = xc.size(-1)
-        call("l3d_layernorm_planes", xc, ln.a_2.detach().contiguous(), ln.b_2.detach().contiguous(), float(ln.eps), xc.numel() // C, C,
+        call("l3d_layernorm_planes", xc, f32a(ln.a_2.detach()), f32a(ln.b_2.detach()), float(ln.eps), xc.numel() // C, C,
              t, None, tag="[values]")
         t._l3d_pending = None
     return t
@@ -159,20 +159,20 @@ class LayerNorm(nn.Module):
         if (x.is_cuda and x.dtype == torch.float32 and C % 4 == 0 and 1 < C <= 2048
                 and not (torch.is_grad_enabled() and (x.requires_grad or self.a_2.requires_grad))):
             from ..models import _fused
-            xc = x.contiguous()
+            xc = f32a(x)                 # l3d_layernorm_planes reads whole rows 16 bytes at a time and refuses a misaligned x / a / b
             y = torch.empty_like(xc)
             rows = xc.numel() // C
             if (_fused.gemm_arith() == "f16x2" and x.dim() == 3 and C % 16 == 0 and C <= 512 and x.size(1) % 256 == 0):
                 # also emit y as the fp16 plane image of the f16x2 conv kernel: the Linear layers that read this output
                 # (_linear_cf) then need no split pass; the image rides on the tensor object
                 img = torch.empty(lib().l3d_f16_image_bytes(1, rows, C), dtype=torch.uint8, device=xc.device)
-                call("l3d_layernorm_planes", xc, self.a_2.detach().contiguous(), self.b_2.detach().contiguous(), float(self.eps), rows, C,
+                call("l3d_layernorm_planes", xc, f32a(self.a_2.detach()), f32a(self.b_2.detach()), float(self.eps), rows, C,
                      y if values else None, img)
                 y._l3d_planes = img
                 if not values:
                     y._l3d_pending = (xc, self)
                 return y
-            call("l3d_layernorm_planes", xc, self.a_2.detach().contiguous(), self.b_2.detach().contiguous(), float(self.eps), rows, C,
+            call("l3d_layernorm_planes", xc, f32a(self.a_2.detach()), f32a(self.b_2.detach()), float(self.eps), rows, C,
                  y, None, tag="[values]")
             return y
         if x.is_cuda:
