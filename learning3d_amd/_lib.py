@@ -1,4 +1,4 @@
-"""ctypes binding of libl3d_hip.so (the C ABI declared in include/*.h).
+"""ctypes binding of libl3d_hip.so (the C ABI declared in include/*.h and, per model, in include/ext/*.h).
 
 The headers are the one description of that boundary: the prototypes, the integer #defines and the l3d_status enum are parsed
 from them when this module is imported (SIGNATURES, PROTOTYPES, CONSTANTS), and `call` is the one launch path built on them.
@@ -88,20 +88,29 @@ def parse_header(text, where="<header>"):
     return protos, consts
 
 
-def _parse_headers():
+def _parse_headers(*subdir):
     protos, consts = {}, {}
-    for path in sorted(glob.glob(os.path.join(INCLUDE_DIR, "*.h"))):
+    for path in sorted(glob.glob(os.path.join(INCLUDE_DIR, *subdir, "*.h"))):
         with open(path) as f:
-            p, c = parse_header(f.read(), os.path.basename(path))
+            p, c = parse_header(f.read(), os.path.join(*subdir, os.path.basename(path)))
         protos.update(p)
         consts.update(c)
     return protos, consts
 
 
+def _argtypes(protos):
+    return {name: [_SCALAR[p.element] if p.indirection == 0 else C.c_void_p for p in proto.params] for name, proto in protos.items()}
+
+
 PROTOTYPES, CONSTANTS = _parse_headers()          # name -> Prototype; L3D_* #defines and l3d_status enumerators -> int
 globals().update(CONSTANTS)                        # _lib.L3D_OK, _lib.L3D_CONV_F16_TWO_PLANE, ...
-# name -> argtypes
-SIGNATURES = {name: [_SCALAR[p.element] if p.indirection == 0 else C.c_void_p for p in proto.params] for name, proto in PROTOTYPES.items()}
+SIGNATURES = _argtypes(PROTOTYPES)                 # name -> argtypes
+# The per-model headers of include/ext/ (l3d_masknet.h), in tables of their own: the same parser, the same library, the same `call`.
+# (Their #defines, if they ever have any, stay in EXT_CONSTANTS: CONSTANTS is what the headers directly under include/ say.)
+EXT_PROTOTYPES, EXT_CONSTANTS = _parse_headers("ext")
+EXT_SIGNATURES = _argtypes(EXT_PROTOTYPES)
+if set(EXT_PROTOTYPES) & set(PROTOTYPES):
+    raise L3DError(f"include/ext/ declares entry points of include/ again: {sorted(set(EXT_PROTOTYPES) & set(PROTOTYPES))}")
 _CALLS = {}                                        # name -> what `call` needs of an entry point; filled by lib()
 
 
@@ -115,9 +124,9 @@ def lib():
                 "(python -m learning3d_amd.build, or __graft_entry__.build()). "
                 "learning3d_amd has no CPU / eager fallback by design.")
         handle = C.CDLL(LIB_PATH)
-        for name, proto in PROTOTYPES.items():
+        for name, proto in (*PROTOTYPES.items(), *EXT_PROTOTYPES.items()):
             fn = getattr(handle, name)          # AttributeError if the ABI drifted
-            fn.argtypes = SIGNATURES[name]
+            fn.argtypes = SIGNATURES[name] if name in SIGNATURES else EXT_SIGNATURES[name]
             fn.restype = proto.restype
             # what `call` wants of a tensor passed for each parameter, worked out once: a dtype (pointer to that element type), None
             # (pointer to anything), or that there is none: _POINTERS (a pointer array: ctypes values only), _BY_VALUE
@@ -206,7 +215,7 @@ def f32a(t):
 
 
 def _bad_argument(name, i, a, want):
-    p = PROTOTYPES[name].params[i]
+    p = (PROTOTYPES.get(name) or EXT_PROTOTYPES[name]).params[i]
     decl = p.ctype + ("" if p.ctype.endswith("*") else " ") + p.name
     if not p.indirection:
         return L3DError(f"{name}: parameter `{decl}` is passed by value, got a tensor")

@@ -9,3 +9,5 @@ from .flownet3d import FlowNet3D, PointNetSetAbstraction, FlowEmbedding, PointNe
 from .pointnetlk import PointNetLK
 from .pcrnet import iPCRNet
 from .curvenet import CurveNet
+from .masknet import MaskNet
+from .segmentation import Segmentation

@@ -521,6 +521,12 @@ def linear_rows(x, lin, relu=False):
     """nn.Linear over a handful of rows x [R, Cin] -> [R, Cout] (+ ReLU): l3d_linear_rows (the weight matrix read once); shapes
     it does not take (Cin % 256 != 0) go through the conv kernels with the rows as the points of one cloud"""
     w, _, b = fold_conv_bn(lin)
+    return rows_affine(x, w, b, relu)
+
+
+def rows_affine(x, w, b=None, relu=False):
+    """linear_rows on a bare weight matrix w [Cout, Cin] (a column slice of a conv's weight: the half of a concatenation that is the
+    same for every point of a cloud, as a per-cloud shift) and bias b [Cout] or None"""
     x = f32c(x)
     R, Cin = x.shape
     if Cin % 256 == 0:

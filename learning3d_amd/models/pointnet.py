@@ -57,8 +57,37 @@ class PointNet(torch.nn.Module):
             return None
         return _fused.checkpointed(self, self._forward_pooled, input_data)
 
+    def forward_parts(self, input_data):
+        """global_feat=False: the two halves of forward()'s concatenation without forming it -- (max over the points [B,emb],
+        point_feature [B,64,N]); conv5's kernel pools in its epilogue.  A consumer whose first layer is a 1x1 conv (models/
+        segmentation.py:22) turns the repeated half into a per-cloud shift.  None when this route does not apply (global_feat=True,
+        CPU tensors, something to differentiate, batch statistics); the caller then uses forward()."""
+        if (self.global_feat or not input_data.is_cuda or input_data.dtype != torch.float32
+                or self.pooling.pool_type != 'max' or not _fused.can_fuse(self, input_data)):
+            return None
+        return _fused.checkpointed(self, self._forward_parts, input_data)
+
     def forward(self, input_data):
         return _fused.checkpointed(self, self._forward, input_data)
+
+    def _forward_parts(self, input_data):
+        channel_last = self.input_shape == "bnc"
+        if input_data.shape[2 if channel_last else 1] != 3:
+            raise RuntimeError("shape of x must be of [Batch x 3 x NumInPoints]")
+        x = input_data
+        stack = self._stack()
+        for i, (conv, bn) in enumerate(stack):
+            w, sc, sh = _fused.fold_conv_bn(conv, bn)
+            if i == len(stack) - 1:
+                return _fused.conv_global_max(x, w, sc, sh, True), point_feature
+            if i == 0 and self.use_bn:
+                # the reference taps layers[1]: bn1's output BEFORE the ReLU (pointnet.py:66)
+                point_feature = _fused.pointwise_conv(x, w, sc, sh, relu=False, channel_last=channel_last)
+                x = torch.relu(point_feature)
+                continue
+            x = _fused.pointwise_conv(x, w, sc, sh, relu=True, channel_last=(channel_last and i == 0))
+            if i == 0:
+                point_feature = x
 
     def _forward_pooled(self, input_data):
         if not _fused.can_fuse(self, input_data):
