@@ -1,4 +1,4 @@
-"""ctypes binding of libl3d_hip.so (the C ABI declared in include/*.h and, per model, in include/ext/*.h).
+"""ctypes binding of libl3d_hip.so (the C ABI declared in include/*.h and, per model, in include/ext/*.h and include/ext/<model>/*.h).
 
 The headers are the one description of that boundary: the prototypes, the integer #defines and the l3d_status enum are parsed
 from them when this module is imported (SIGNATURES, PROTOTYPES, CONSTANTS), and `call` is the one launch path built on them.
@@ -92,7 +92,7 @@ def _parse_headers(*subdir):
     protos, consts = {}, {}
     for path in sorted(glob.glob(os.path.join(INCLUDE_DIR, *subdir, "*.h"))):
         with open(path) as f:
-            p, c = parse_header(f.read(), os.path.join(*subdir, os.path.basename(path)))
+            p, c = parse_header(f.read(), os.path.relpath(path, INCLUDE_DIR))
         protos.update(p)
         consts.update(c)
     return protos, consts
@@ -111,6 +111,12 @@ EXT_PROTOTYPES, EXT_CONSTANTS = _parse_headers("ext")
 EXT_SIGNATURES = _argtypes(EXT_PROTOTYPES)
 if set(EXT_PROTOTYPES) & set(PROTOTYPES):
     raise L3DError(f"include/ext/ declares entry points of include/ again: {sorted(set(EXT_PROTOTYPES) & set(PROTOTYPES))}")
+# Later models keep their header in a directory of their own, include/ext/<model>/ (masknet2/l3d_masknet2.h), and their entry points in
+# a third pair of tables: EXT_* stays what the headers directly under include/ext/ say (MaskNet's two entry points).
+MODEL_PROTOTYPES, MODEL_CONSTANTS = _parse_headers("ext", "*")
+MODEL_SIGNATURES = _argtypes(MODEL_PROTOTYPES)
+if set(MODEL_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES)):
+    raise L3DError(f"include/ext/*/ declares entry points again: {sorted(set(MODEL_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES)))}")
 _CALLS = {}                                        # name -> what `call` needs of an entry point; filled by lib()
 
 
@@ -124,9 +130,9 @@ def lib():
                 "(python -m learning3d_amd.build, or __graft_entry__.build()). "
                 "learning3d_amd has no CPU / eager fallback by design.")
         handle = C.CDLL(LIB_PATH)
-        for name, proto in (*PROTOTYPES.items(), *EXT_PROTOTYPES.items()):
+        for name, proto in (*PROTOTYPES.items(), *EXT_PROTOTYPES.items(), *MODEL_PROTOTYPES.items()):
             fn = getattr(handle, name)          # AttributeError if the ABI drifted
-            fn.argtypes = SIGNATURES[name] if name in SIGNATURES else EXT_SIGNATURES[name]
+            fn.argtypes = next(table[name] for table in (SIGNATURES, EXT_SIGNATURES, MODEL_SIGNATURES) if name in table)
             fn.restype = proto.restype
             # what `call` wants of a tensor passed for each parameter, worked out once: a dtype (pointer to that element type), None
             # (pointer to anything), or that there is none: _POINTERS (a pointer array: ctypes values only), _BY_VALUE
@@ -215,7 +221,7 @@ def f32a(t):
 
 
 def _bad_argument(name, i, a, want):
-    p = (PROTOTYPES.get(name) or EXT_PROTOTYPES[name]).params[i]
+    p = (PROTOTYPES.get(name) or EXT_PROTOTYPES.get(name) or MODEL_PROTOTYPES[name]).params[i]
     decl = p.ctype + ("" if p.ctype.endswith("*") else " ") + p.name
     if not p.indirection:
         return L3DError(f"{name}: parameter `{decl}` is passed by value, got a tensor")

@@ -11,3 +11,4 @@ from .pcrnet import iPCRNet
 from .curvenet import CurveNet
 from .masknet import MaskNet
 from .segmentation import Segmentation
+from .masknet2 import MaskNet2
