@@ -3,11 +3,10 @@
  * one launch.  Same conventions as l3d_hip.h: device pointers, fp32 unless said otherwise, every call asynchronous on `stream`,
  * status codes of l3d_status (null pointer / non-positive size -> -1, a shape the kernels are not built for -> -2, both before
  * any launch).
- * Per-model headers live here, in include/ext/: _lib.py reads them into EXT_PROTOTYPES / EXT_SIGNATURES, beside the tables of the
- * headers directly under include/. */
+ * A per-model header like l3d_curvenet.h and l3d_registration.h: _lib.py reads every header of include/ into one table. */
 #ifndef L3D_MASKNET_H
 #define L3D_MASKNET_H
-#include "../l3d_hip.h"
+#include "l3d_hip.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

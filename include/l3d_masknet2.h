@@ -5,7 +5,7 @@
  * not built for -> -2, both before any launch). */
 #ifndef L3D_MASKNET2_H
 #define L3D_MASKNET2_H
-#include "../../l3d_hip.h"
+#include "l3d_hip.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -1,4 +1,4 @@
-"""ctypes binding of libl3d_hip.so (the C ABI declared in include/*.h and, per model, in include/ext/*.h and include/ext/<model>/*.h).
+"""ctypes binding of libl3d_hip.so (the C ABI declared in include/*.h: l3d_hip.h and one header per later model).
 
 The headers are the one description of that boundary: the prototypes, the integer #defines and the l3d_status enum are parsed
 from them when this module is imported (SIGNATURES, PROTOTYPES, CONSTANTS), and `call` is the one launch path built on them.
@@ -88,35 +88,30 @@ def parse_header(text, where="<header>"):
     return protos, consts
 
 
-def _parse_headers(*subdir):
-    protos, consts = {}, {}
-    for path in sorted(glob.glob(os.path.join(INCLUDE_DIR, *subdir, "*.h"))):
+def _parse_headers(directory):
+    """-> ({name: Prototype}, {NAME: int}) of every *.h in `directory`; an entry point declared by two headers, or a constant they
+    give two values, raises, naming both"""
+    protos, consts, declared_in = {}, {}, {}
+    for path in sorted(glob.glob(os.path.join(directory, "*.h"))):
+        where = os.path.basename(path)
         with open(path) as f:
-            p, c = parse_header(f.read(), os.path.relpath(path, INCLUDE_DIR))
+            p, c = parse_header(f.read(), where)
+        for name in p:
+            if name in protos:
+                raise L3DError(f"{name} is declared by {declared_in[name]} and by {where}")
+        for name, value in c.items():
+            if consts.get(name, value) != value:
+                raise L3DError(f"{name} is {consts[name]} in {declared_in[name]} and {value} in {where}")
+        declared_in.update(dict.fromkeys((*p, *c), where))
         protos.update(p)
         consts.update(c)
     return protos, consts
 
 
-def _argtypes(protos):
-    return {name: [_SCALAR[p.element] if p.indirection == 0 else C.c_void_p for p in proto.params] for name, proto in protos.items()}
-
-
-PROTOTYPES, CONSTANTS = _parse_headers()          # name -> Prototype; L3D_* #defines and l3d_status enumerators -> int
-globals().update(CONSTANTS)                        # _lib.L3D_OK, _lib.L3D_CONV_F16_TWO_PLANE, ...
-SIGNATURES = _argtypes(PROTOTYPES)                 # name -> argtypes
-# The per-model headers of include/ext/ (l3d_masknet.h), in tables of their own: the same parser, the same library, the same `call`.
-# (Their #defines, if they ever have any, stay in EXT_CONSTANTS: CONSTANTS is what the headers directly under include/ say.)
-EXT_PROTOTYPES, EXT_CONSTANTS = _parse_headers("ext")
-EXT_SIGNATURES = _argtypes(EXT_PROTOTYPES)
-if set(EXT_PROTOTYPES) & set(PROTOTYPES):
-    raise L3DError(f"include/ext/ declares entry points of include/ again: {sorted(set(EXT_PROTOTYPES) & set(PROTOTYPES))}")
-# Later models keep their header in a directory of their own, include/ext/<model>/ (masknet2/l3d_masknet2.h), and their entry points in
-# a third pair of tables: EXT_* stays what the headers directly under include/ext/ say (MaskNet's two entry points).
-MODEL_PROTOTYPES, MODEL_CONSTANTS = _parse_headers("ext", "*")
-MODEL_SIGNATURES = _argtypes(MODEL_PROTOTYPES)
-if set(MODEL_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES)):
-    raise L3DError(f"include/ext/*/ declares entry points again: {sorted(set(MODEL_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES)))}")
+PROTOTYPES, CONSTANTS = _parse_headers(INCLUDE_DIR)   # name -> Prototype; L3D_* #defines and l3d_status enumerators -> int
+globals().update(CONSTANTS)                        # _lib.L3D_OK, _lib.L3D_CONV_F16_TWO_PLANE, _lib.L3D_SELF_ATTN_TQ, ...
+SIGNATURES = {name: [_SCALAR[p.element] if p.indirection == 0 else C.c_void_p for p in proto.params]
+              for name, proto in PROTOTYPES.items()}                                                  # name -> argtypes
 _CALLS = {}                                        # name -> what `call` needs of an entry point; filled by lib()
 
 
@@ -130,9 +125,9 @@ def lib():
                 "(python -m learning3d_amd.build, or __graft_entry__.build()). "
                 "learning3d_amd has no CPU / eager fallback by design.")
         handle = C.CDLL(LIB_PATH)
-        for name, proto in (*PROTOTYPES.items(), *EXT_PROTOTYPES.items(), *MODEL_PROTOTYPES.items()):
+        for name, proto in PROTOTYPES.items():
             fn = getattr(handle, name)          # AttributeError if the ABI drifted
-            fn.argtypes = next(table[name] for table in (SIGNATURES, EXT_SIGNATURES, MODEL_SIGNATURES) if name in table)
+            fn.argtypes = SIGNATURES[name]
             fn.restype = proto.restype
             # what `call` wants of a tensor passed for each parameter, worked out once: a dtype (pointer to that element type), None
             # (pointer to anything), or that there is none: _POINTERS (a pointer array: ctypes values only), _BY_VALUE
@@ -221,7 +216,7 @@ def f32a(t):
 
 
 def _bad_argument(name, i, a, want):
-    p = (PROTOTYPES.get(name) or EXT_PROTOTYPES.get(name) or MODEL_PROTOTYPES[name]).params[i]
+    p = PROTOTYPES[name].params[i]
     decl = p.ctype + ("" if p.ctype.endswith("*") else " ") + p.name
     if not p.indirection:
         return L3DError(f"{name}: parameter `{decl}` is passed by value, got a tensor")

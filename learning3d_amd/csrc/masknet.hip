@@ -10,7 +10,7 @@
 //                    largest key, then a prefix-sum compaction in ascending point index (ties: lowest index first).
 #include "common.h"
 #include "split_bf16.h"          // f32x4
-#include "../../include/ext/l3d_masknet.h"
+#include "../../include/l3d_masknet.h"
 
 #define MT_KC 16                 // input channels per k-chunk of w4 staged through LDS (C % 16 == 0: every chunk is full)
 #define MT_PTS 256               // points per workgroup: 4 waves x 64

@@ -18,7 +18,7 @@
 //                              with the row maximum known in closed form.
 #include "common.h"
 #include "split_bf16.h"          // f32x16
-#include "../../include/ext/masknet2/l3d_masknet2.h"
+#include "../../include/l3d_masknet2.h"
 
 // ------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float mish1(float x)

@@ -127,6 +127,24 @@ def fold_conv_bn(conv, bn=None):
     return cached(conv.__dict__, "_l3d_fold", [conv.weight, conv.bias] + bn_state(bn), build, extra=(bn is not None,))
 
 
+def conv_column_blocks(conv, bn, at, scale_block=None):
+    """A 1x1 conv over the concatenation [a ; b] of `at` channels a and the rest b, as two convs: -> (w[:, :at], w[:, at:], scale,
+    shift), both blocks contiguous, with w, scale and shift those of fold_conv_bn(conv, bn).  When one half is the same vector for
+    every point of a cloud (a pooled feature repeated over the points), its block times that vector is a per-cloud shift
+    (rows_affine) and the conv runs over the other half's columns alone.  scale_block = 0 or 1: the BN scale multiplied into the
+    rows of that block (needs a bn).  Cached on the conv like fold_conv_bn's result; treat the returned tensors as read-only."""
+    if scale_block is not None and bn is None:
+        raise ValueError("scale_block names the block that takes the BatchNorm scale: there is none without a bn")
+
+    def build():
+        w, scale, shift = fold_conv_bn(conv, bn)
+        blocks = [w[:, :at], w[:, at:]]
+        if scale_block is not None:
+            blocks[scale_block] = scale[:, None] * blocks[scale_block]
+        return blocks[0].contiguous(), blocks[1].contiguous(), scale, shift
+    return cached(conv.__dict__, "_l3d_blocks", [conv.weight, conv.bias] + bn_state(bn), build, extra=(at, scale_block, bn is not None))
+
+
 def _stochastic_or_batch_dependent(module):
     """BatchNorm on batch statistics (train mode, or no running statistics: torch normalises such a layer by the batch in eval
     mode too) or an active Dropout: forward is not a pure function of inputs + parameters"""
@@ -148,6 +166,11 @@ def can_fuse(module, *tensors):
                                     any(p.requires_grad for p in module.parameters())):
         return False
     return True
+
+
+def fusable(module, *tensors):
+    """can_fuse on device fp32 tensors: the gate of a forward whose fused route has no CPU, other-dtype or differentiable form"""
+    return all(t.is_cuda and t.dtype == torch.float32 for t in tensors) and can_fuse(module, *tensors)
 
 
 _TLS = threading.local()
@@ -368,39 +391,34 @@ def pointwise_conv_f16(x_planes, B, N, w_planes, Cin, Cout, scale=None, shift=No
     two = unscaled and Cout % 256 == 0 and N % 256 == 0
     if unscaled and not two:
         raise ValueError("the two-plane conv kernel takes Cout % 256 == 0 and N % 256 == 0")
+    dev = x_planes.device
+    # the image's residual plane is unscaled (edgeconv_forward(..., planes=True, unscaled=True)): two weight planes
+    tag, flags = ("[two-plane]", L3D_CONV_F16_TWO_PLANE) if two else ("", 0)
     if out_planes:
         if shift is not None and shift.dim() != 1:
             raise ValueError("plane output takes a per-channel shift only")
-        dev = x_planes.device
         obs = _plane_obs(scale, shift, dev)
-        img = torch.empty(lib().l3d_f16_image_bytes(1, B * N, Cout), dtype=torch.uint8, device=dev)
-        _conv_f16("[planes]" + ("[two-plane]" if two else ""), x_planes, w_planes, scale, shift, 0, B, Cin, Cout, N,
-                  relu, flags=(L3D_CONV_F16_TWO_PLANE | L3D_CONV_F16_OUT_UNSCALED) if two else 0, img=img, obs=obs)
-        return img
-    bstride = Cout if (shift is not None and shift.dim() == 2) else 0
-    y = torch.empty((B, Cout, N), dtype=torch.float32, device=x_planes.device)
-    if residual is not None:
-        # y = residual + layer(x): the sublayer's residual connection in the GEMM's epilogue
-        if amax is not None or tuple(residual.shape) != (B, Cout, N) or not (Cout % 256 == 0 and N % 256 == 0):
-            raise ValueError("residual epilogue: residual [B,Cout,N], Cout % 256 == 0, N % 256 == 0, no absmax")
-        _conv_f16("[residual]" + ("[two-plane]" if two else ""), x_planes, w_planes, scale, shift, bstride, B, Cin,
-                  Cout, N, relu, flags=L3D_CONV_F16_TWO_PLANE if two else 0, y=y, residual=f32c(residual))
-        return y
-    if two and amax is not None:
-        _conv_f16("[absmax][two-plane]", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu,
-                  flags=L3D_CONV_F16_TWO_PLANE, y=y, amax=amax[0], amax_cdiv=int(amax[1]))
-        return y
-    if unscaled:
-        # the image's residual plane is unscaled (edgeconv_forward(..., planes=True, unscaled=True)): two weight planes
-        _conv_f16("[two-plane]", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu, flags=L3D_CONV_F16_TWO_PLANE, y=y,
-                  span=stage("conv5_kernel"))               # the launch alone (bench.py's live timing)
-        return y
-    if amax is not None:
-        _conv_f16("[absmax]", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu, y=y,
-                  amax=amax[0], amax_cdiv=int(amax[1]))
-        return y
-    _conv_f16("", x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu, y=y)
-    return y
+        out = torch.empty(lib().l3d_f16_image_bytes(1, B * N, Cout), dtype=torch.uint8, device=dev)
+        tag, bstride, outputs = "[planes]" + tag, 0, dict(img=out, obs=obs)
+        if two:
+            flags |= L3D_CONV_F16_OUT_UNSCALED
+    else:
+        bstride = Cout if (shift is not None and shift.dim() == 2) else 0
+        out = torch.empty((B, Cout, N), dtype=torch.float32, device=dev)
+        outputs = dict(y=out)
+        if residual is not None:
+            # y = residual + layer(x): the sublayer's residual connection in the GEMM's epilogue
+            if amax is not None or tuple(residual.shape) != (B, Cout, N) or not (Cout % 256 == 0 and N % 256 == 0):
+                raise ValueError("residual epilogue: residual [B,Cout,N], Cout % 256 == 0, N % 256 == 0, no absmax")
+            tag = "[residual]" + tag
+            outputs["residual"] = f32c(residual)
+        elif amax is not None:
+            tag = "[absmax]" + tag
+            outputs.update(amax=amax[0], amax_cdiv=int(amax[1]))
+        elif two:
+            outputs["span"] = stage("conv5_kernel")             # the launch alone (bench.py's live timing)
+    _conv_f16(tag, x_planes, w_planes, scale, shift, bstride, B, Cin, Cout, N, relu, flags=flags, **outputs)
+    return out
 
 
 def first_layer_f16_planes(x, w, shift, relu, channel_last):

@@ -73,7 +73,7 @@ class PointNetMask(nn.Module):
 
     def fusable(self, *tensors):
         """device fp32 tensors, BatchNorm on running statistics, nothing to differentiate"""
-        return FUSED and all(t.is_cuda and t.dtype == torch.float32 for t in tensors) and _fused.can_fuse(self, *tensors)
+        return FUSED and _fused.fusable(self, *tensors)
 
     def forward(self, template, source):
         if self.fusable(template, source):
@@ -96,19 +96,16 @@ class PointNetMask(nn.Module):
         C0 = w0.shape[0]
         if g.shape[1] + Ct != w0.shape[1]:
             raise RuntimeError(f"h3 takes {w0.shape[1]} channels, the feature model gives {Ct} + {g.shape[1]}")
-        store = self.__dict__.setdefault("_l3d_images", {})
-
-        def halves():
-            w = w0.detach().reshape(C0, -1).float()
-            return w[:, :Ct].contiguous(), w[:, Ct:].contiguous()
-        wt, wg = _fused.cached(store, "h3.0", [w0], halves, extra=(Ct,))
+        wt, wg, _, b0 = _fused.conv_column_blocks(conv0, None, Ct)
         # the source half of h3[0], the same for every point of a cloud: a per-cloud shift [B,C0]
-        shift = _fused.rows_affine(g, wg, conv0.bias.detach() if conv0.bias is not None else None)
+        shift = _fused.rows_affine(g, wg, b0)
         w2, _, b2 = _fused.fold_conv_bn(conv2)
         w4, _, b4 = _fused.fold_conv_bn(conv4)
         C2, C4 = w2.shape[0], w4.shape[0]
         if (_fused.gemm_arith() == "f16x2" and _fused.SPLIT_BF16
                 and all(_fused.f16_eligible(ci, co, N) for ci, co in ((Ct, C0), (C0, C2), (C2, C4)))):
+            store = self.__dict__.setdefault("_l3d_images", {})
+
             # keyed by the parameters themselves (a derived tensor's address can come back after a rebuild)
             def image(name, src, w):
                 return _fused.cached(store, name, [src], lambda: _fused.split_weights_f16(w), extra=(Ct,))

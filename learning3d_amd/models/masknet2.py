@@ -44,7 +44,7 @@ SCORES_FP64_FOR_GRAD = True  # Self_Attn, when its output is differentiated: q^T
 
 def _fusable(module, *tensors):
     """device fp32 tensors, BatchNorm on running statistics, nothing to differentiate"""
-    return FUSED and all(t.is_cuda and t.dtype == torch.float32 for t in tensors) and _fused.can_fuse(module, *tensors)
+    return FUSED and _fused.fusable(module, *tensors)
 
 
 def mish_(x):
@@ -265,11 +265,7 @@ class PointNetMask(nn.Module):
         w0 = h0.conv.weight
         if Ct + g.shape[1] != w0.shape[1]:
             raise RuntimeError(f"h3 takes {w0.shape[1]} channels, the feature model gives {Ct} + {g.shape[1]}")
-
-        def halves():
-            w, scale, shift = _fused.fold_conv_bn(h0.conv, h0.bn)
-            return w[:, :Ct].contiguous(), (scale[:, None] * w[:, Ct:]).contiguous(), scale, shift
-        wt, wg, scale, shift = _fused.cached(h0.__dict__, "_l3d_halves", [w0] + _fused.bn_state(h0.bn), halves, extra=(Ct,))
+        wt, wg, scale, shift = _fused.conv_column_blocks(h0.conv, h0.bn, Ct, scale_block=1)      # wg carries the BN scale
         x = _fused.pointwise_conv(feats, wt, scale, _fused.rows_affine(g, wg, shift), relu=False)
         if h0.active == True:      # noqa: E712
             mish_(x)

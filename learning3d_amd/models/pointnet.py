@@ -70,66 +70,48 @@ class PointNet(torch.nn.Module):
     def forward(self, input_data):
         return _fused.checkpointed(self, self._forward, input_data)
 
-    def _forward_parts(self, input_data):
-        channel_last = self.input_shape == "bnc"
-        if input_data.shape[2 if channel_last else 1] != 3:
+    def _fused_stack(self, x, channel_last, tap, pool):
+        """The folded stack on the conv kernels: x [B,N,3] (channel_last, consumed as it lies: no transpose copy) or [B,3,N] ->
+        (the last layer's output [B,emb,N], or with `pool` its maximum over the points [B,emb] from conv5's epilogue;
+        with `tap` the first layer's output [B,64,N], else None)."""
+        if x.shape[2 if channel_last else 1] != 3:
             raise RuntimeError("shape of x must be of [Batch x 3 x NumInPoints]")
-        x = input_data
+        point_feature = None
         stack = self._stack()
         for i, (conv, bn) in enumerate(stack):
             w, sc, sh = _fused.fold_conv_bn(conv, bn)
-            if i == len(stack) - 1:
-                return _fused.conv_global_max(x, w, sc, sh, True), point_feature
-            if i == 0 and self.use_bn:
+            if pool and i == len(stack) - 1:
+                x = _fused.conv_global_max(x, w, sc, sh, True)
+            elif i == 0 and tap and self.use_bn:
                 # the reference taps layers[1]: bn1's output BEFORE the ReLU (pointnet.py:66)
                 point_feature = _fused.pointwise_conv(x, w, sc, sh, relu=False, channel_last=channel_last)
                 x = torch.relu(point_feature)
-                continue
-            x = _fused.pointwise_conv(x, w, sc, sh, relu=True, channel_last=(channel_last and i == 0))
-            if i == 0:
-                point_feature = x
+            else:
+                x = _fused.pointwise_conv(x, w, sc, sh, relu=True, channel_last=(channel_last and i == 0))
+                if i == 0 and tap:
+                    point_feature = x
+        return x, point_feature
+
+    def _forward_parts(self, input_data):
+        return self._fused_stack(input_data, self.input_shape == "bnc", tap=True, pool=True)
 
     def _forward_pooled(self, input_data):
         if not _fused.can_fuse(self, input_data):
             return self._forward(input_data).max(dim=2)[0]
-        channel_last = self.input_shape == "bnc"
-        if input_data.shape[2 if channel_last else 1] != 3:
-            raise RuntimeError("shape of x must be of [Batch x 3 x NumInPoints]")
-        x = input_data
-        stack = self._stack()
-        for i, (conv, bn) in enumerate(stack):
-            w, sc, sh = _fused.fold_conv_bn(conv, bn)
-            if i == len(stack) - 1:
-                return _fused.conv_global_max(x, w, sc, sh, True)
-            x = _fused.pointwise_conv(x, w, sc, sh, relu=True, channel_last=(channel_last and i == 0))
+        return self._fused_stack(input_data, self.input_shape == "bnc", tap=False, pool=True)[0]
 
     def _forward(self, input_data):
-        if self.input_shape == "bnc":
-            num_points = input_data.shape[1]
-            input_data = input_data.permute(0, 2, 1)
-        else:
-            num_points = input_data.shape[2]
-        if input_data.shape[1] != 3:
-            raise RuntimeError("shape of x must be of [Batch x 3 x NumInPoints]")
-
-        output = input_data
+        channel_last = self.input_shape == "bnc"
+        num_points = input_data.shape[1 if channel_last else 2]
         if _fused.can_fuse(self, input_data) and input_data.is_cuda:
-            # "bnc" input is consumed channel-last directly (no transpose copy)
-            channel_last = self.input_shape == "bnc"
-            x = input_data.permute(0, 2, 1) if channel_last else input_data
-            for i, (conv, bn) in enumerate(self._stack()):
-                w, sc, sh = _fused.fold_conv_bn(conv, bn)
-                if i == 0 and not self.global_feat and self.use_bn:
-                    # the reference taps layers[1]: bn1's output BEFORE the ReLU (pointnet.py:66)
-                    point_feature = _fused.pointwise_conv(x, w, sc, sh, relu=False, channel_last=channel_last)
-                    x = torch.relu(point_feature)
-                    continue
-                x = _fused.pointwise_conv(x, w, sc, sh, relu=True, channel_last=(channel_last and i == 0))
-                if i == 0 and not self.global_feat:
-                    point_feature = x
-            output = x
+            output, point_feature = self._fused_stack(input_data, channel_last, tap=not self.global_feat, pool=False)
         else:
             from ._train import conv_bn_act, hip_layers_ok
+            if channel_last:
+                input_data = input_data.permute(0, 2, 1)
+            if input_data.shape[1] != 3:
+                raise RuntimeError("shape of x must be of [Batch x 3 x NumInPoints]")
+            output = input_data
             if hip_layers_ok(input_data):
                 # autograd is live: every layer on the HIP conv / dgrad / wgrad kernels (_train.py), BatchNorm with batch
                 # statistics in train mode and running statistics in eval mode

@@ -34,8 +34,7 @@ class Segmentation(nn.Module):
 
     def forward(self, input_data):
         fm = self.feature_model
-        if (FUSED and hasattr(fm, "forward_parts") and input_data.is_cuda and input_data.dtype == torch.float32
-                and _fused.can_fuse(self, input_data)):
+        if FUSED and hasattr(fm, "forward_parts") and _fused.fusable(self, input_data):
             with on_device_of(input_data):
                 out = _fused.run_guarded(input_data.device, lambda: self._forward_fused(input_data))
             if out is not None:
@@ -54,12 +53,7 @@ class Segmentation(nn.Module):
             return None
         pooled, point_feature = parts                   # [B,emb], [B,64,N]
         emb = pooled.shape[1]
-        w1, scale, shift = _fused.fold_conv_bn(self.conv1, self.bn1)
-
-        def halves():
-            return w1[:, :emb].contiguous(), w1[:, emb:].contiguous()
-        # keyed by the parameter itself (the folded w1's address can come back after a re-fold)
-        wg, wp = _fused.cached(self.__dict__.setdefault("_l3d_images", {}), "conv1", [self.conv1.weight], halves, extra=(emb,))
+        wg, wp, scale, shift = _fused.conv_column_blocks(self.conv1, self.bn1, emb)
         # the global half comes first in this concatenation: a per-cloud shift [B,512]
         cloud_shift = scale * _fused.rows_affine(pooled, wg) + shift
         x = _fused.pointwise_conv(point_feature, wp, scale, cloud_shift, relu=True)

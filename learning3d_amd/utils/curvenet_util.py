@@ -111,10 +111,8 @@ def _fused():
 
 def _fusable(module, *tensors):
     """May `module` launch the fused kernels on these tensors: device fp32, BatchNorm on running statistics, nothing to
-    differentiate (models/_fused.can_fuse)."""
-    if not FUSED_WALK or not all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
-        return False
-    return _fused().can_fuse(module, *tensors)
+    differentiate (models/_fused.fusable)."""
+    return FUSED_WALK and _fused().fusable(module, *tensors)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -60,7 +60,7 @@ def dev():
 @pytest.fixture(scope="module")
 def consts():
     from learning3d_amd import _lib
-    return _lib.MODEL_CONSTANTS["L3D_SELF_ATTN_TQ"], _lib.MODEL_CONSTANTS["L3D_SELF_ATTN_TK"]
+    return _lib.L3D_SELF_ATTN_TQ, _lib.L3D_SELF_ATTN_TK
 
 
 @pytest.fixture(scope="module")

@@ -58,7 +58,7 @@ def test_prototypes_are_read_from_the_headers():
     for name, (restype, argtypes) in want.items():
         assert _lib.PROTOTYPES[name].restype is restype, name
         assert _lib.SIGNATURES[name] == argtypes, name
-    assert len(_lib.SIGNATURES) == 107
+    assert len(_lib.SIGNATURES) == 112
     par = {name: [(p.ctype, p.name) for p in proto.params] for name, proto in _lib.PROTOTYPES.items()}
     assert par["l3d_knn_graph"][4] == ("int64_t *", "idx") and par["l3d_knn_graph"][5] == ("l3d_stream_t", "stream")
     assert par["l3d_bmm_f32"][1] == ("const long *", "a_strides") and par["l3d_bmm_f32"][11] == ("float", "alpha")
@@ -76,6 +76,24 @@ def test_prototypes_are_read_from_the_headers():
                 "int l3d_f(int (*cb)(int));"):
         with pytest.raises(_lib.L3DError, match=r"t\.h:3"):
             _lib.parse_header("\n\n" + bad + "\n", "t.h")
+
+
+def test_an_entry_point_declared_by_two_headers_raises(tmp_path):
+    """One table for every header of include/: the same name in two headers is an error that names both, not a silent overwrite."""
+    from learning3d_amd import _lib
+    (tmp_path / "a.h").write_text("#define L3D_A 1\nint l3d_f(const float *x, int n, l3d_stream_t stream);\n")
+    (tmp_path / "b.h").write_text("#define L3D_B 2\nint l3d_g(int n);\n")
+    protos, consts = _lib._parse_headers(str(tmp_path))
+    assert sorted(protos) == ["l3d_f", "l3d_g"] and consts == {"L3D_A": 1, "L3D_B": 2}
+    (tmp_path / "b.h").write_text("#define L3D_B 2\nint l3d_f(int n);\n")
+    with pytest.raises(_lib.L3DError, match=r"l3d_f.*a\.h.*b\.h"):
+        _lib._parse_headers(str(tmp_path))
+    # the constants share one namespace too: the same value twice is fine, two values are not
+    (tmp_path / "b.h").write_text("#define L3D_A 1\nint l3d_g(int n);\n")
+    assert _lib._parse_headers(str(tmp_path))[1] == {"L3D_A": 1}
+    (tmp_path / "b.h").write_text("#define L3D_A 3\nint l3d_g(int n);\n")
+    with pytest.raises(_lib.L3DError, match=r"L3D_A is 1 in a\.h and 3 in b\.h"):
+        _lib._parse_headers(str(tmp_path))
 
 
 def test_call_checks_tensor_dtypes_before_devices():

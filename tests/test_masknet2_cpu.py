@@ -184,23 +184,23 @@ def test_unequal_sizes_against_restated_find_mask(golden):
 def test_header_table():
     from learning3d_amd import _lib
     P, I, L = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-    assert _lib.MODEL_SIGNATURES == {"l3d_mish": [P, L, P, P],
-                                     "l3d_self_attention_shared": [P, P, I, I, I, P, P],
-                                     "l3d_outer_softmax_mix": [P, P, P, I, I, P, P, P]}
-    assert all(p.restype is I for p in _lib.MODEL_PROTOTYPES.values())
-    par = {n: [(p.ctype, p.name) for p in proto.params] for n, proto in _lib.MODEL_PROTOTYPES.items()}
+    want = {"l3d_mish": [P, L, P, P],
+            "l3d_self_attention_shared": [P, P, I, I, I, P, P],
+            "l3d_outer_softmax_mix": [P, P, P, I, I, P, P, P]}
+    assert {n: _lib.SIGNATURES[n] for n in want} == want
+    assert all(_lib.PROTOTYPES[n].restype is I for n in want)
+    par = {n: [(p.ctype, p.name) for p in _lib.PROTOTYPES[n].params] for n in want}
     assert par["l3d_mish"] == [("const float *", "x"), ("long", "count"), ("float *", "y"), ("l3d_stream_t", "stream")]
     assert par["l3d_self_attention_shared"] == [("const float *", "q"), ("const float *", "beta"), ("int", "B"), ("int", "D"), ("int", "N"),
                                                 ("float *", "out"), ("l3d_stream_t", "stream")]
     assert par["l3d_outer_softmax_mix"] == [("const float *", "px"), ("const float *", "py"), ("const float *", "beta"), ("int", "B"),
                                             ("int", "C"), ("float *", "outx"), ("float *", "outy"), ("l3d_stream_t", "stream")]
-    assert _lib.MODEL_CONSTANTS["L3D_SELF_ATTN_TQ"] % 32 == 0 and _lib.MODEL_CONSTANTS["L3D_SELF_ATTN_TK"] % 32 == 0
-    assert not set(_lib.MODEL_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES))
+    assert _lib.L3D_SELF_ATTN_TQ % 32 == 0 and _lib.L3D_SELF_ATTN_TK % 32 == 0
     handle = ctypes.CDLL(_lib.LIB_PATH)
-    assert all(hasattr(handle, n) for n in _lib.MODEL_SIGNATURES)
+    assert all(hasattr(handle, n) for n in want)
     _lib.lib()
-    assert all(n in _lib._CALLS for n in _lib.MODEL_SIGNATURES)
-    with pytest.raises(_lib.L3DError, match="float32"):                  # the one typed path serves this table, too
+    assert all(n in _lib._CALLS for n in want)
+    with pytest.raises(_lib.L3DError, match="float32"):                  # the one typed path serves them, too
         _lib.call("l3d_mish", torch.zeros(4, dtype=torch.float64), 4, torch.zeros(4))
 
 

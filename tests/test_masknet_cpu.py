@@ -1,5 +1,5 @@
 """MaskNet and Segmentation without a GPU: the public names, the reference's state_dict keys, the op-sequence forward against the
-reference's fp64 results (tests/golden/make_golden_masknet.py), the ext header's ctypes table, and the numpy model of
+reference's fp64 results (tests/golden/make_golden_masknet.py), l3d_masknet.h's entries in the ctypes table, and the numpy model of
 l3d_mask_select's rank rule that the GPU tests compare the kernel with.
 
 Bars: a whole model's output is held to 4 x the reference's own fp32-to-fp64 gap on the same input (GAP_FACTOR, the project's bar
@@ -153,20 +153,20 @@ def test_segmentation_cpu_forward_against_fp64(golden):
         assert ratio <= GAP_FACTOR
 
 
-def test_ext_header_table():
+def test_masknet_header_entries():
     from learning3d_amd import _lib
     P, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    assert _lib.EXT_SIGNATURES == {"l3d_mask_tail": [P, P, P, P, P, I, I, I, I, P, P],
-                                   "l3d_mask_select": [P, P, I, I, I, F, P, P, P, P]}
-    assert all(p.restype is I for p in _lib.EXT_PROTOTYPES.values())
-    par = [(p.ctype, p.name) for p in _lib.EXT_PROTOTYPES["l3d_mask_select"].params]
+    want = {"l3d_mask_tail": [P, P, P, P, P, I, I, I, I, P, P], "l3d_mask_select": [P, P, I, I, I, F, P, P, P, P]}
+    assert {n: _lib.SIGNATURES[n] for n in want} == want
+    assert all(_lib.PROTOTYPES[n].restype is I for n in want)
+    par = [(p.ctype, p.name) for p in _lib.PROTOTYPES["l3d_mask_select"].params]
     assert par[5] == ("float", "threshold") and par[6] == ("int64_t *", "idx") and par[8] == ("int32_t *", "count")
-    assert len(_lib.SIGNATURES) == 107 and not set(_lib.EXT_SIGNATURES) & set(_lib.SIGNATURES)
+    assert len(_lib.SIGNATURES) == 112
     handle = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(handle, "l3d_mask_tail") and hasattr(handle, "l3d_mask_select")
-    _lib.lib()                                                           # resolves the ext symbols, too
+    _lib.lib()                                                           # resolves MaskNet's symbols, too
     assert "l3d_mask_tail" in _lib._CALLS and "l3d_mask_select" in _lib._CALLS
-    with pytest.raises(_lib.L3DError, match="float32"):                  # the one typed path serves the ext table: dtype checks
+    with pytest.raises(_lib.L3DError, match="float32"):                  # the one typed path serves them: dtype checks
         _lib.call("l3d_mask_select", torch.zeros(1, 4, dtype=torch.float64), torch.zeros(1, 4, 3), 1, 4, 1, 0.5,
                   torch.zeros(1, 1, dtype=torch.int64), torch.zeros(1, 1, 3), torch.zeros(1, dtype=torch.int32))
 

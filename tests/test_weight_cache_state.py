@@ -34,6 +34,24 @@ def _sa():
     return PointNetSetAbstraction(npoint=16, radius=0.4, nsample=16, in_channel=3, mlp=[32, 32, 64], group_all=False)
 
 
+class _ConvBN(torch.nn.Module):
+    """a 1x1 conv over a 24-channel concatenation (8 + 16) with the BatchNorm behind it, and one (`plain`) with none"""
+
+    def __init__(self):
+        super().__init__()
+        self.conv, self.bn = torch.nn.Conv1d(24, 16, 1), torch.nn.BatchNorm1d(16)
+        self.plain = torch.nn.Conv1d(24, 16, 1)
+
+
+def _blocks_without_bn(n):
+    """A conv with no BatchNorm behind it, as MaskNet's h3[0] is split: its blocks stay in their cache slot across the change (nothing
+    else writes it).  A BatchNorm-only change leaves them where they were, as it must; the fold of the model's other layer, a cache
+    of its own on another conv, is what such a change moves."""
+    wa, wb, scale, bias = _fused.conv_column_blocks(n.plain, None, 8)
+    assert scale is None
+    return (wa, wb, bias) + _fused.fold_conv_bn(n.conv, n.bn)
+
+
 # name -> (model factory, probe: model -> tuple of the cached tensors an eval forward reads)
 PROBES = {
     "fold_conv_bn": (lambda: DGCNN(emb_dims=64), lambda n: _fused.fold_conv_bn(n.conv5, n.bn5)),
@@ -42,6 +60,9 @@ PROBES = {
     "sa_mlp3_params": (_sa, lambda n: _fused.sa_mlp3_params(list(n.mlp_convs), list(n.mlp_bns), torch.device("cpu"))[:1]),
     "prnet._layer_params": (lambda: prnet.DGCNN(emb_dims=64),
                             lambda n: n._layer_params("2", n.conv2, n.bn2, True)[:2] + n._layer_params("5", n.conv5, n.bn5, False)[:2]),
+    "conv_column_blocks": (_ConvBN, lambda n: _fused.conv_column_blocks(n.conv, n.bn, 8)),
+    "conv_column_blocks[scale_block=1]": (_ConvBN, lambda n: _fused.conv_column_blocks(n.conv, n.bn, 8, scale_block=1)),
+    "conv_column_blocks[no bn]": (_ConvBN, _blocks_without_bn),
 }
 
 
@@ -116,6 +137,11 @@ def test_cached_parameters_follow_state_changes(probe, change):
     # the change moved the cached values well beyond fp32 rounding: otherwise a stale cache would pass
     moved = max(float((a - b).abs().max() / b.abs().max().clamp_min(1e-30)) for a, b in zip(before, want))
     assert moved > 1e-5, (probe, change, moved)
+
+
+def test_conv_column_blocks_without_bn_has_no_scale_to_fold():
+    with pytest.raises(ValueError, match="scale_block"):
+        _fused.conv_column_blocks(torch.nn.Conv1d(24, 16, 1), None, 8, scale_block=1)
 
 
 def test_fold_follows_the_running_statistics_of_a_train_mode_forward():
