@@ -20,6 +20,9 @@ def mean_shift(template, source, p0_zero_mean, p1_zero_mean):
     template_mean, source_mean = eye_t, eye_s
     if p1_zero_mean and not p0_zero_mean:
         raise ValueError("p1_zero_mean=True needs p0_zero_mean=True (the source's matrix is built from the template's mean)")
+    # torch sums a strided cloud (a transposed [B,3,N] buffer) in another order than a dense one: the centre, and behind it every
+    # iterate of the loop, would depend on how the caller's tensor lies.  The clouds are made dense first (no copy when they are).
+    template, source = template.contiguous(), source.contiguous()
     if p0_zero_mean:
         p0_m = template.mean(dim=1)
         template_mean = _translation(eye_t, p0_m)
