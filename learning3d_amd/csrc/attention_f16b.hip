@@ -128,13 +128,7 @@ __global__ __launch_bounds__(512) void attention_f16b_kernel(const float *__rest
     const bool v_item = v_d < D;
     const bool v_vec8 = (M & 7) == 0 && (v_bs & 3) == 0 && ((((size_t)v) & 15) == 0);     // every 8-key run of a V row: two aligned 16-byte loads
     float kr[8], vr[8];
-    // Ablation builds of tools/probe_attention_f16b.hip (timing only, results are garbage): AB_NOLOAD skips the tiles' global loads,
-    // AB_NOSTAGE also their splits and LDS writes, AB_NOSOFTMAX the exp2 / split work on the probabilities, AB_NOLDSREAD reads
-    // one operand cell per phase instead of all of them.
     auto load_tile = [&](int key0) {
-#if defined(AB_NOLOAD) || defined(AB_NOSTAGE)
-        return;
-#endif
         // Nothing here is conditional per lane: a conditional load is an exec-masked branch with a wait at its join, and the tile's
         // loads then queue up one round trip behind the other instead of flying together under the previous tile's MFMAs (the form
         // this replaced: `key < M ? src[..] : 0` and a per-lane choice between the 16-byte and the scalar V loads).  Indices beyond
@@ -175,9 +169,6 @@ __global__ __launch_bounds__(512) void attention_f16b_kernel(const float *__rest
         }
     };
     auto store_tile = [&](int stage) {
-#ifdef AB_NOSTAGE
-        return;
-#endif
         unsigned char *base = ab_lds + stage * STAGE;
         if (k_item) {
             u32x4 hv, mv;
@@ -234,14 +225,10 @@ __global__ __launch_bounds__(512) void attention_f16b_kernel(const float *__rest
         for (int r = 0; r < 16; r++) { S[r] = 0.f; S1[r] = 0.f; }
 #pragma unroll
         for (int ks = 0; ks < KS; ks += 2) {
-#ifdef AB_NOLDSREAD
-            const f16x8 Kh = Qm[ks], Km = Qh[ks], Kh1 = Qm[ks + 1], Km1 = Qh[ks + 1];
-#else
             const f16x8 Kh = *(const f16x8 *)(base + ka_off + ks * 1024);
             const f16x8 Km = *(const f16x8 *)(base + KPL + ka_off + ks * 1024);
             const f16x8 Kh1 = *(const f16x8 *)(base + ka_off + (ks + 1) * 1024);
             const f16x8 Km1 = *(const f16x8 *)(base + KPL + ka_off + (ks + 1) * 1024);
-#endif
             S = __builtin_amdgcn_mfma_f32_32x32x16_f16(Km, Qh[ks], S, 0, 0, 0);
             S1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Km1, Qh[ks + 1], S1, 0, 0, 0);
             S = __builtin_amdgcn_mfma_f32_32x32x16_f16(Kh, Qm[ks], S, 0, 0, 0);
@@ -280,16 +267,6 @@ __global__ __launch_bounds__(512) void attention_f16b_kernel(const float *__rest
         }
         const float shift = 12.0f - m_run;                        // p 2^12 = exp2(S sc2 - m + 12): one fma + v_exp_f32 per value
         float lsum = 0.f;
-#ifdef AB_NOSOFTMAX
-        for (int s2 = 0; s2 < 2; s2++) {
-            u32x4 hv, mv;
-            for (int e = 0; e < 4; e++) { hv[e] = __float_as_uint(S[8 * s2 + 2 * e]); mv[e] = __float_as_uint(S[8 * s2 + 2 * e + 1]); lsum += S[8 * s2 + e]; }
-            Ph[s2] = __builtin_bit_cast(f16x8, hv);
-            Pm[s2] = __builtin_bit_cast(f16x8, mv);
-        }
-        l_run += lsum + shift;
-        return;
-#endif
 #pragma unroll
         for (int s2 = 0; s2 < 2; s2++) {
             u32x4 hv, mv;
@@ -316,12 +293,8 @@ __global__ __launch_bounds__(512) void attention_f16b_kernel(const float *__rest
             f16x8 Vh[ND], Vm[ND];
 #pragma unroll
             for (int dt = 0; dt < ND; dt++) {
-#ifdef AB_NOLDSREAD
-                Vh[dt] = Qh[dt]; Vm[dt] = Qm[dt];
-#else
                 Vh[dt] = *(const f16x8 *)(base + va_off + s2 * (2 * VBLK) + dt * 512);
                 Vm[dt] = *(const f16x8 *)(base + VPL + va_off + s2 * (2 * VBLK) + dt * 512);
-#endif
             }
 #pragma unroll
             for (int dt = 0; dt < ND; dt++) O[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Vm[dt], Ph[s2], O[dt], 0, 0, 0);
@@ -361,9 +334,7 @@ __global__ __launch_bounds__(512) void attention_f16b_kernel(const float *__rest
             if (more) store_tile(st_next);
             score(S, st_cur);
         }
-#ifndef AB_NOBARRIER
         __syncthreads();                                          // tile kt+1 is in place; tile kt-1's stage is free
-#endif
         const int tmp = st_prev;
         st_prev = st_cur;
         st_cur = st_next;

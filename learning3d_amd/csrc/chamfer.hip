@@ -19,9 +19,6 @@
 #define CTILE 2048      // candidates per LDS tile, shared by the 4 waves (32 KiB)
 #define CWAVES 4        // waves per workgroup: each scans 1/4 of every tile for the SAME 64*QPL queries
 #define CUNROLL 8
-#ifndef CH_SMALL_TILE
-#define CH_SMALL_TILE 0      // 1: 1024-candidate tiles when neither cloud is longer (LABLOG R6.2: co-resident with the kNN kernel, and slower)
-#endif
 #define CHAMFER_LL_BLOCKS 64                                  // l3d_chamfer_loss_local_mb's workgroups
 #define CHAMFER_LL_WS_BYTES (16 + CHAMFER_LL_BLOCKS * 16)
 
@@ -174,11 +171,11 @@ __device__ __forceinline__ void chamfer_loss_tail(double sq, unsigned *__restric
 // tried this with __threadfence() in front of the ticket and lost 4 us per step (LABLOG R3.10): an agent-scope release fence
 // writes the XCD's whole L2 back; a write-through store of the 8 bytes that matter does not.  The separate loss kernel was 7 us
 // on the Chamfer branch's critical path in front of EdgeConv (launch + L2 turn-around for ~1 us of work).
-// PTILE: candidates per LDS tile, 2048 in the product.  With 1024 (20 KB with the merge arrays; -DCH_SMALL_TILE=1) a workgroup fits on
+// PTILE: candidates per LDS tile, 2048 (CTILE) in every launch.  With 1024 (20 KB with the merge arrays) a workgroup fits on
 // a CU BESIDE two of knn_mfma_kernel's (2 x 69.6 KB at N = 1024), which the 36 KB of a 2048-candidate tile does not -- the two kernels
 // of the bench step's front, launched side by side on two streams, take turns on a CU (24.5 + 16.7 us alone, 39.5 together).  Measured
-// (LABLOG R6.2): co-resident, the step is 1.3 % SLOWER (281.5 vs 277.9 us, four interleaved pairs on one box) -- the kNN kernel is the
-// front's critical path and the Chamfer waves beside it take its issue slots.  Not the default.
+// (LABLOG R6.2, and again beside the one-round kNN in R7.1): co-resident, the step is 1.3 % SLOWER (281.5 vs 277.9 us, four interleaved
+// pairs on one box) -- the kNN kernel is the front's critical path and the Chamfer waves beside it take its issue slots.  Not instantiated.
 template <bool LOSS, int PTILE>
 __global__ __launch_bounds__(64 * CWAVES) void chamfer_fwd_packed_kernel(const float *__restrict__ xyz1,
                                                                          const float *__restrict__ xyz2, int N, int M,
@@ -334,12 +331,8 @@ extern "C" int l3d_chamfer_forward_variant(const float *xyz1, const float *xyz2,
     const long wgs2 = (long)l3d_divup(mx, 128) * B * 2;
     if (l3d_chamfer_forward_mode == 2 || (l3d_chamfer_forward_mode == 1 && wgs2 * CWAVES >= 1024)) {
         dim3 grid(l3d_divup(mx, 128), B, 2);
-        if (mx <= 1024 && CH_SMALL_TILE)
-            hipLaunchKernelGGL((chamfer_fwd_packed_kernel<false, 1024>), grid, dim3(64 * CWAVES), 0, (hipStream_t)stream, xyz1, xyz2, N, M,
-                               dist1, dist2, idx1, idx2, (unsigned *)nullptr, (double *)nullptr, (float *)nullptr);
-        else
-            hipLaunchKernelGGL((chamfer_fwd_packed_kernel<false, CTILE>), grid, dim3(64 * CWAVES), 0, (hipStream_t)stream, xyz1, xyz2, N, M,
-                               dist1, dist2, idx1, idx2, (unsigned *)nullptr, (double *)nullptr, (float *)nullptr);
+        hipLaunchKernelGGL((chamfer_fwd_packed_kernel<false, CTILE>), grid, dim3(64 * CWAVES), 0, (hipStream_t)stream, xyz1, xyz2, N, M,
+                           dist1, dist2, idx1, idx2, (unsigned *)nullptr, (double *)nullptr, (float *)nullptr);
     } else if (wgs2 * 2 >= 8192) {
         dim3 grid(l3d_divup(mx, 128), B, 2);
         hipLaunchKernelGGL(chamfer_fwd_kernel<2>, grid, dim3(64 * CWAVES), 0, (hipStream_t)stream, xyz1,
@@ -382,12 +375,8 @@ extern "C" int l3d_chamfer_forward_loss(const float *xyz1, const float *xyz2, in
     const long wgs2 = (long)l3d_divup(mx, 128) * B * 2;
     if ((long)N * M < (1L << 24) && wgs2 * CWAVES >= 1024) {
         dim3 grid(l3d_divup(mx, 128), B, 2);
-        if (mx <= 1024 && CH_SMALL_TILE)
-            hipLaunchKernelGGL((chamfer_fwd_packed_kernel<true, 1024>), grid, dim3(64 * CWAVES), 0, (hipStream_t)stream, xyz1, xyz2, N, M, dist1,
-                               dist2, idx1, idx2, (unsigned *)ws, partial, loss);
-        else
-            hipLaunchKernelGGL((chamfer_fwd_packed_kernel<true, CTILE>), grid, dim3(64 * CWAVES), 0, (hipStream_t)stream, xyz1, xyz2, N, M, dist1,
-                               dist2, idx1, idx2, (unsigned *)ws, partial, loss);
+        hipLaunchKernelGGL((chamfer_fwd_packed_kernel<true, CTILE>), grid, dim3(64 * CWAVES), 0, (hipStream_t)stream, xyz1, xyz2, N, M, dist1,
+                           dist2, idx1, idx2, (unsigned *)ws, partial, loss);
         return l3d_check_launch();
     }
     const int rc = l3d_chamfer_forward_variant(xyz1, xyz2, B, N, M, dist1, dist2, idx1, idx2, 1, stream);

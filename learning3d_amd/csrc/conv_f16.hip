@@ -38,7 +38,6 @@
 // 128 x 256 workgroups, two per CU, which do hide the epilogue (99 us); those with W fragments straight from L2 (110 us);
 // all 14 reads ahead of the first MFMA (105 us); first-product fragments read across the barrier (105 us); LDS bank
 // padding of the regions (worth 25 % in the bare read + MFMA loop, nothing here); non-temporal epilogue stores (-1 us).
-#include <cstdlib>
 #include <type_traits>
 #include "common.h"
 #include "split_bf16.h"          // f32x4 / f32x16 typedefs
@@ -397,13 +396,6 @@ __global__ __launch_bounds__(512) void conv_f16_kernel(const uint4 *__restrict__
         }
     }
     auto issue_one = [&](int stage, int i) {
-#ifdef CF_ABL      // timing ablation (results are garbage): bit 0 = no W pieces after the prologue, bit 1 = no x pieces
-        {
-            int q_ = wave * NPIECE + i;
-            if (q_ >= NWP + NXP) q_ -= NXP;
-            if (((CF_ABL & 1) && q_ < NWP) || ((CF_ABL & 2) && q_ >= NWP)) return;
-        }
-#endif
         __builtin_amdgcn_global_load_lds((cf_gbl_ptr_t)src[i], (cf_lds_ptr_t)(lds + stage * STAGE + dst[i]), 16, 0, 0);
         src[i] += stride[i];
     };
@@ -450,14 +442,7 @@ __global__ __launch_bounds__(512) void conv_f16_kernel(const uint4 *__restrict__
         const bool more = kc + 2 < nk;
         CFT(2)
         const unsigned char *base = lds + stage * STAGE;
-#if defined(CF_ABL) && (CF_ABL & 8)     // timing ablation: the twelve fragments are read in the first chunk only
-        static_assert(true, "");
         f16x8 A[2][NPW], Bf[4][2];
-        if (kc == 0 || ((const volatile int *)winv)[0] == 0x7fffffff)
-#else
-        f16x8 A[2][NPW], Bf[4][2];
-#endif
-        {
 #pragma unroll
         for (int p = 0; p < 2; p++)
 #pragma unroll
@@ -466,7 +451,6 @@ __global__ __launch_bounds__(512) void conv_f16_kernel(const uint4 *__restrict__
         for (int p = NPW - 1; p >= 0; p--)
 #pragma unroll
             for (int a = 0; a < 2; a++) A[a][p] = *(const f16x8 *)(base + a_off + a * 512 + p * 2 * WR);
-        }
         // three products, smallest first: M h, Hs m', H h
         // The five DMA instructions of chunk kc+2 are spread over the chunk's 24 MFMAs, one behind every fifth: the CU's
         // vector-memory path takes 16 cycles per 1 KB instruction and all eight waves share it -- issued as one block behind
@@ -682,20 +666,10 @@ __global__ __launch_bounds__(512) void conv_f16_kernel(const uint4 *__restrict__
                 // stores its dirty lines are still being written back while the NEXT launches run -- the step's EdgeConv kernel is
                 // 128 us behind a kNN launch and 140 us behind this kernel (tools/ec_instep_probe.py: its dependent index / coordinate
                 // gathers queue behind the write-back).  Nontemporal stores cost this kernel 1.5 us and give EdgeConv 3-5 back.
-#if defined(CF_ABL) && (CF_ABL & 4)     // timing ablation: no output stores (a store that never fires keeps the accumulators alive)
-                if (v == 12345.678f) yb[(size_t)co * N + n0 + wn * 128 + c * 32 + (lane & 31)] = v;
-#else
-#ifndef CF_STORE
-#define CF_STORE 1     // the two-plane instantiation's output stores: 0 plain, 1 nt (default), 2 sc1 (write-through, agent), 3 sc0 sc1 (system)
-#endif
+                // (LABLOG R6.1, conv5 alone: nontemporal 280.1 us, plain 279.6, write-through sc1 287.9, sc0 sc1 288.0)
                 float *dst_ = &yb[(size_t)co * N + n0 + wn * 128 + c * 32 + (lane & 31)];
-                if constexpr (NPW == 2 && !AMAX && !RESID && !SHIFTN) {
-                    if (CF_STORE == 1) __builtin_nontemporal_store(v, dst_);
-                    else if (CF_STORE == 2) __hip_atomic_store(dst_, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else if (CF_STORE == 3) __hip_atomic_store(dst_, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    else *dst_ = v;
-                } else *dst_ = v;
-#endif
+                if constexpr (NPW == 2 && !AMAX && !RESID && !SHIFTN) __builtin_nontemporal_store(v, dst_);
+                else *dst_ = v;
                 // (asm: left to the compiler the maxima are re-associated into ONE tree behind the last store, every v alive until then)
                 if constexpr (AMAX) {
                     asm volatile("v_max_f32_e64 %0, %0, |%1|" : "+v"(amax_run) : "v"(v));
@@ -731,12 +705,6 @@ __global__ __launch_bounds__(512) void conv_f16_kernel(const uint4 *__restrict__
     }
 }
 
-#ifdef CF_PERSIST    // tools/experiments/conv_f16_persist.inc: persistent two-tile form with an LDS-transposed 16-byte epilogue (LABLOG R6.1; measured, slower in the step)
-#include "../../tools/experiments/conv_f16_persist.inc"
-#endif
-#ifdef CF_HALF       // tools/experiments/conv_f16_half.inc: 256-thread workgroups, two per CU (LABLOG R4.4; measured, not faster)
-#include "../../tools/experiments/conv_f16_half.inc"
-#endif
 // Sizes of the plane images (common.h: l3d_f16_plane_bytes / l3d_f16_act_bytes / l3d_conv_f16_weight_bytes), one exported spelling:
 // kind 0 = ONE fp16 plane of a [rows][cols] matrix in the tiled layout; 1 = an activation image (h | m' planes + 16 bytes:
 // 2^-T, scratch); 2 = a weight image of [rows = Cout][cols = Cin] (H | Hs | M planes + 16 bytes: 2^-S, |w| maximum, row-sum maximum)
@@ -868,29 +836,7 @@ static int cf_launch(const void *x_planes, const void *w_planes, const float *sc
     }
     if (two_plane) {
         if (narrow || group || amax_out || ypool || out_img || !y) return L3D_ERR_UNSUPPORTED;
-#ifdef CF_HALF
-        hipLaunchKernelGGL(conv_f16_half_kernel, dim3((unsigned)((size_t)(N / CFH_TN) * (Cout / CFH_TM) * B)), dim3(256), CFH_LDS, st,
-                           (const uint4 *)xp, (const uint4 *)(xp + xpb), (const uint4 *)wp, (const uint4 *)(wp + 2 * wpb),
-                           (const float *)(wp + 3 * wpb), (const float *)(xp + 2 * xpb), scale, shift, shift_bstride, B, Cin, Cout, N, relu, y);
-#else
-#ifdef CF_PERSIST
-        {
-            // persistent form: one workgroup per CU (a multiple of 8, so that a workgroup's tiles stay on its XCD's Cout group)
-            static bool ok = [] { return hipFuncSetAttribute((const void *)conv_f16_persist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                             CFP_LDS) == hipSuccess; }();
-            static const bool off = [] { const char *e = getenv("L3D_CONV5_PERSIST"); return e && e[0] == '0'; }();
-            const int ntiles = (int)grid.x;
-            if (ok && !off && Cin >= 32) {
-                const int wgs = ntiles < 256 ? ntiles : 256;
-                hipLaunchKernelGGL(conv_f16_persist_kernel, dim3(wgs), block, CFP_LDS, st, (const uint4 *)xp, (const uint4 *)(xp + xpb),
-                                   (const uint4 *)wp, (const uint4 *)(wp + 2 * wpb), (const float *)(wp + 3 * wpb), (const float *)(xp + 2 * xpb),
-                                   scale, shift, shift_bstride, B, Cin, Cout, N, relu, y, ntiles);
-                return l3d_check_launch();
-            }
-        }
-#endif
         hipLaunchKernelGGL((conv_f16_kernel<false, false, false, 2>), grid, block, 3 * (4 * CF_TM * 16 + 4 * CF_TN * 16), st, CF_ARGS);
-#endif
         return l3d_check_launch();
     }
     if (narrow && group)         hipLaunchKernelGGL((conv_f16_kernel<true, false, true>), grid, block, nlds, st, CF_ARGS);

@@ -37,13 +37,7 @@
 #define CS_TK 16
 #define CS_REGION (256 * 16 + 64)           // bytes of one (plane, kg) region (+64: write-side bank skew)
 #define CS_BUF (12 * CS_REGION)             // W: 6 regions, X: 6 regions
-#ifndef CS_INTERLEAVE
-#define CS_INTERLEAVE 1
-#endif
-#ifndef CS_STAGES
-#define CS_STAGES 3                        // LDS chunk buffers of the 256x256 kernel (2: staging after the MFMAs; 3: inside them)
-#endif
-#define CS_LDS (CS_STAGES * CS_BUF)
+#define CS_LDS (3 * CS_BUF)                 // three LDS chunk buffers: the next-but-one chunk is staged inside the MFMA stream
 
 // ---------------------------------------------------------------------------------------------
 // Weight (or activation) splitter: src [R][C] fp32 row-major -> dst [ceil(C/16)][3][2][R][8] bf16.
@@ -160,7 +154,6 @@ __global__ __launch_bounds__(512) void conv_split_kernel(const void *__restrict_
     const int a_off = frag_kg + (wm * 128 + (lane & 31)) * 16;                       // + a*32*16 + p*2*REGION
     const int b_off = 6 * CS_REGION + frag_kg + (wn * 64 + (lane & 31)) * 16;        // + c*32*16 + p*2*REGION
 
-#if CS_STAGES == 3
     // Three LDS chunk buffers: chunk kc+2 is loaded at the top of chunk kc and split / written to LDS in
     // the MIDDLE of chunk kc's MFMA stream (its buffer was last read in chunk kc-1), so the staging tail
     // no longer sits between the last MFMA and the barrier with the matrix pipe idle.
@@ -204,80 +197,18 @@ __global__ __launch_bounds__(512) void conv_split_kernel(const void *__restrict_
                 if (more) CS_STORE_LDS(wbuf);
             }
             if (pa == 0) {                  // ... its split VALU / LDS stores issued between the h plane's 24 MFMAs
-#if CS_INTERLEAVE
 #pragma unroll
                 for (int i = 0; i < 24; i++) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
                     if (i % 4 == 3) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
                 }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
         __syncthreads();
         buf = buf == 2 ? 0 : buf + 1;
     }
-#else
-    CS_LOAD_GLOBAL(0);
-    CS_STORE_LDS(0);
-    __syncthreads();
-
-#ifdef CS_TIMING
-    unsigned long long tacc[5] = {0, 0, 0, 0, 0}, tprev = __builtin_amdgcn_s_memtime();
-#define CS_TSTAMP(i) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); tacc[i] += now_ - tprev; tprev = now_; } while (0)
-#else
-#define CS_TSTAMP(i)
-#endif
-    for (int kc = 0; kc < nk; kc++) {
-        const int buf = kc & 1;
-        const bool more = kc + 1 < nk;
-        if (!(CS_PROBE & 1) && more) CS_LOAD_GLOBAL(kc + 1);
-        CS_TSTAMP(0);
-        const unsigned char *base = lds + buf * CS_BUF;
-        bf16x8 A[4][3], Bf[2][3];
-#pragma unroll
-        for (int p = 0; p < 3; p++) {
-            if ((CS_PROBE & 8) && kc > 0) break;
-#pragma unroll
-            for (int a = 0; a < 4; a++) A[a][p] = *(const bf16x8 *)(base + a_off + a * 512 + p * 2 * CS_REGION);
-#pragma unroll
-            for (int c = 0; c < 2; c++) Bf[c][p] = *(const bf16x8 *)(base + b_off + c * 512 + p * 2 * CS_REGION);
-        }
-#ifdef CS_TIMING
-        asm volatile("s_waitcnt lgkmcnt(0)");
-        CS_TSTAMP(1);
-#endif
-        // six products per tile, smallest terms first
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                f32x16 d = acc[a][c];
-                if (CS_PROBE & 4) {
-                    asm volatile("" ::"v"(A[a][0]), "v"(A[a][1]), "v"(A[a][2]), "v"(Bf[c][0]), "v"(Bf[c][1]), "v"(Bf[c][2]));
-                    continue;
-                }
-                d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][2], Bf[c][0], d, 0, 0, 0);
-                d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][0], Bf[c][2], d, 0, 0, 0);
-                d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][1], Bf[c][1], d, 0, 0, 0);
-                d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][1], Bf[c][0], d, 0, 0, 0);
-                d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][0], Bf[c][1], d, 0, 0, 0);
-                d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][0], Bf[c][0], d, 0, 0, 0);
-                acc[a][c] = d;
-            }
-        CS_TSTAMP(2);
-        if (!(CS_PROBE & 2) && more) CS_STORE_LDS(buf ^ 1);
-        CS_TSTAMP(3);
-        if (!(CS_PROBE & 16)) __syncthreads();
-        CS_TSTAMP(4);
-    }
-#ifdef CS_TIMING
-    if ((t & 63) == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z < 4)      // scratch area past the output
-        for (int i = 0; i < 5; i++)
-            ((unsigned long long *)(y + (size_t)Bn * Cout * N))[(blockIdx.z * 8 + wave) * 5 + i] = tacc[i];
-#endif
-#endif
 #undef CS_LOAD_GLOBAL
 #undef CS_STORE_LDS
 

@@ -47,9 +47,6 @@
 #include "split_bf16.h"      // f32x2 / f32x4 typedefs
 
 #define EF_V2 1
-#ifndef EF_SPLIT_MIX
-#define EF_SPLIT_MIX 1
-#endif
 // Layer 4's weight fragments (128 KB as two planes) are copied to LDS once per workgroup and read from there by every tile -- a
 // ds_read_b128 beside the MFMA stream costs about half of a global_load_dwordx4 (LABLOG R2.2: +19 vs +43 cycles per 5 MFMAs) and
 // layer 4 issues 128 of them per tile.
@@ -103,20 +100,13 @@ typedef EfBase ef_rsrc_t;
 // layers therefore issue their MFMAs as volatile inline asm with the homes fixed by constraints:
 //     accumulators  VGPRs ("+v")  -- the finish VALU reads and writes them in place, no copies;
 //     B operands    AGPRs ("a")   -- the split activation planes are only ever MFMA operands (<= 240 registers);
-//     A operands    VGPRs ("v")   -- weight fragments arrive by global_load.
+//     A operands    AGPRs ("a")   -- weight fragments arrive by global_load, which writes AGPRs directly.
 // Volatile asm statements keep their program order, so the interleave of finish work and MFMAs below is the issue
 // order; the compiler still places the fragment loads, address arithmetic and s_waitcnt (asm operands are uses).
 // What it no longer does is pad MFMA hazards: every read of an accumulator by VALU code is >= 5 MFMAs after the
 // MFMA that wrote it (see the unit order), and the two places where that does not hold by construction carry s_nop.
 // ---------------------------------------------------------------------------------------------
-#ifndef EF_AHOME
-#define EF_AHOME 1          // weight fragments (MFMA A operand): 0 = VGPRs, 1 = AGPRs (global_load writes them directly)
-#endif
-#if EF_AHOME
-#define EF_ACON "a"
-#else
-#define EF_ACON "v"
-#endif
+#define EF_ACON "a"          // weight fragments (MFMA A operand) live in AGPRs: global_load writes them directly
 __device__ __forceinline__ void ef_mfma_init(f32x4 &d, const u32x4 &a, const f16x8 &b, const f32x4 &c)
 {
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&v"(d) : EF_ACON(a), "a"(b), "v"(c));
@@ -165,32 +155,15 @@ __device__ __forceinline__ float ef_dpp_max_x2(float give, float keep)
 //   h = f16(a c) (c = 2^-S: the product is exact, one rounding), r = a c - h (exact), m' = f16(r 2^12)
 __device__ __forceinline__ void ef_split_pair(float a0, float a1, float c, uint32_t &h, uint32_t &m)
 {
-    float r0, r1;
     // accumulators are already in plane units (c == 1): round the pair, subtract the rounded halves back (exact), round the
-    // residuals.  s_nop: VALU write -> SDWA read of the same VGPR, not seen by the hazard recogniser inside asm.
-    float f0, f1;
+    // residuals.
+    (void)c;
     asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(a0), "v"(a1));
-#if EF_SPLIT_MIX
     // three instructions per value pair instead of six: v_fma_mixlo/hi_f16 form a * 1.0 - f32(h half) in fp32 (exact: a - h is
-    // representable) and round it to the fp16 half of m in the same instruction -- the same bits as convert, subtract, convert
+    // representable) and round it to the fp16 half of m in the same instruction -- the same bits as convert, subtract, convert.
+    // s_nop: VALU write -> read of the same VGPR, not seen by the hazard recogniser inside asm.
     asm volatile("s_nop 0\n\tv_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(m) : "v"(a0), "v"(h));
     asm volatile("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(m) : "v"(a1), "v"(h));
-    (void)c; (void)f0; (void)f1; (void)r0; (void)r1;
-    return;
-#endif
-    asm volatile("v_cvt_f32_f16_e32 %0, %1" : "=v"(f0) : "v"(h));
-    asm volatile("s_nop 0\n\tv_cvt_f32_f16_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(f1) : "v"(h));
-    asm volatile("v_sub_f32 %0, %1, %2" : "=v"(r0) : "v"(a0), "v"(f0));
-    asm volatile("v_sub_f32 %0, %1, %2" : "=v"(r1) : "v"(a1), "v"(f1));
-    asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(m) : "v"(r0), "v"(r1));
-    (void)c;
-    return;
-    asm volatile("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(a0), "v"(c));
-    asm volatile("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(a1), "v"(c));
-    asm volatile("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r0) : "v"(a0), "v"(c), "v"(h));
-    asm volatile("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r1) : "v"(a1), "v"(c), "v"(h));
-    asm volatile("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(m) : "v"(r0), "s"(4096.0f));
-    asm volatile("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(m) : "v"(r1), "s"(4096.0f));
 }
 
 // Lane-constant context of the pooled stores.  q = lane & 3 (neighbour slot inside the quad); after the transposing
@@ -416,17 +389,7 @@ __device__ __forceinline__ void ef_pair(int mp, const EfNext &nx, const f16x8 (&
                 if constexpr (s == 0 && prod == 0) ef_mfma_init(acc[mm][t], R.a[0][pa], bop, R.bv[mm]);
                 else ef_mfma_acc(acc[mm][t], R.a[0][pa], bop);
                 constexpr int slot = (r * 3 + prod) * MT + t;
-#ifdef EF_NOFINISH                                                     // timing experiment: accumulators kept alive, no finish work
-                if constexpr (slot == 0) {
-#pragma unroll
-                    for (int kk = 0; kk < 2; kk++)
-#pragma unroll
-                        for (int tt = 0; tt < MT; tt++) asm volatile("" ::"v"(hp[kk][tt]));
-                }
-                if constexpr (false)
-#else
                 if constexpr (slot < NSL)
-#endif
                     ef_static_for<slot * NU / NSL, (slot + 1) * NU / NSL>([&](auto u) {
                         ef_micro<MT, PREV_LAST, PREV_RAW, PLANES, decltype(u)::value>(hp, po_prev, T, ch_prev, L, c_prev, ovf);
                     });
@@ -729,11 +692,7 @@ __global__ __launch_bounds__(256, 1) void EF_KERNEL(const float *__restrict__ xy
     // point to before pair 6), waited for before pair 7, where every count is known, instead of behind the loop's back edge.
     f16x8 dummy[1][2][MT];
     u32x4 X;                                                     // the 16 bytes on their way from LDS to the image
-#ifdef EF_NT_OUT      // experiment (LABLOG R5.6): the pooled planes leave through nontemporal stores
-#define EF_ST16(ptr, val) __builtin_nontemporal_store(val, (u32x4 *)(ptr))
-#else
 #define EF_ST16(ptr, val) (*(u32x4 *)(ptr) = (val))
-#endif
     auto st_a = [&](int c) { EF_ST16(img_pt + (size_t)((c >> 1) * 64 + (c & 1) * 16 + (lane >> 2)) * row_bytes, X); EF_PIN(); };
     auto st_b = [&](int m0) {                                    // chunk of pairs m0, m0 + 1: lane -> slot, plane, cell row, point
         const int row = ((lane >> 4) & 1) * 64 + (EC_C1 + EC_C2 + EC_C3) / 8 + 4 * (m0 + (lane >> 5)) + ((lane >> 2) & 3);

@@ -49,9 +49,6 @@ __device__ __forceinline__ unsigned fk_lds_off(const void *p)
 #else
 #define FKM(i)
 #endif
-#ifndef FK_ABL
-#define FK_ABL 0      // timing ablations (tools/build_variant_lib.py; results are garbage): 1 no rank phase, 2 nothing reaches the bound, 4 one sweep, 8 no epilogue
-#endif
 #define FK_QT 128                          // queries per workgroup (4 column blocks of 32)
 #define FK_STAGE 33792                     // 2 key halves x 2 planes x 8 octets x 64 rows x 16 B (128 keys x 64 channels) + 1 KB: the tile's aux
 #define FK_AUXT 256                        // floats of aux per 128-key tile: -|x_row|^2 x 128 | 2^-T | max |x_row| | (unused)
@@ -333,7 +330,7 @@ __global__ __launch_bounds__(512) void featknn_kernel(const uint4 *__restrict__ 
             else if (NBF == 1 || set == 0) products(Bh[0], Bm[0]);
             else products(Bh[NBF - 1], Bm[NBF - 1]);
 
-            if (ch == nch - 1 && !(FK_ABL & 8)) {
+            if (ch == nch - 1) {
                 // ---- epilogue of key tile kt: p0 = -xx_j + 2 <x_i, x_j> for this lane's 2 x 16 candidates (the reference's pd = p0 - xx_i is
                 // formed for the collected candidates only: x -> fl(x - xx_i) is monotone, so selecting on p0 selects the same set)
                 // The tile's aux arrived as a DMA piece; read with compiler-visible loads, the compiler orders them behind EVERY LDS DMA it has
@@ -375,7 +372,7 @@ __global__ __launch_bounds__(512) void featknn_kernel(const uint4 *__restrict__ 
                         unsigned m = 0;
 #pragma unroll
                         for (int r = 0; r < 16; r++) m |= pd[r] >= thr ? (1u << r) : 0u;
-                        if (!(FK_ABL & 16) && __builtin_amdgcn_ballot_w64(m != 0) != 0) {
+                        if (__builtin_amdgcn_ballot_w64(m != 0) != 0) {
                             // Every LDS access of the collection as inline asm, for the reason the aux reads are: the compiler puts
                             // s_waitcnt vmcnt(0) in front of any LDS access that may alias a DMA destination -- here, behind the pieces just
                             // issued for the next unit.  The 16 values go to this wave's dump rows (a lane's column), a hit's value comes
@@ -464,23 +461,21 @@ __global__ __launch_bounds__(512) void featknn_kernel(const uint4 *__restrict__ 
             __syncthreads();
             const float *t4 = tv + ql * 5;
             thr = fmaxf(fminf(fminf(t4[0], t4[1]), fminf(t4[2], t4[3])) - margin, -3.0e38f);     // -inf (fewer than KC real candidates): every finite one
-            if (FK_ABL & 2) thr = INFINITY;
         }
     };
     FKM(1)
     run_sweep(std::integral_constant<int, 0>{});
     FKM(3)
-    if (!(FK_ABL & 4)) run_sweep(std::integral_constant<int, 1>{});
+    run_sweep(std::integral_constant<int, 1>{});
     FKM(4)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // (the asm LDS writes of the collection are not the compiler's to wait for)
     __syncthreads();
 
     // ---- rank: four threads per query, thread part ranks keys part, part + 4, ...; a key of rank r < k gives idx[q][r]
-    if (FK_ABL & 32) return;
     if constexpr (LL) {
         const int rq = t >> 2, part = t & 3, gq = q0 + rq;
         const int M = qcnt[rq];
-        const bool ranked = gq < N && M <= CAP && !(FK_ABL & 1);
+        const bool ranked = gq < N && M <= CAP;
         int *outl = (int *)lds;                                 // [128][k] ranks -> indices, in the idle stages; written out coalesced below
         // own keys part, part + 4, ... in registers, ONE pass over the list; no branches: a compare written with && / || became an
         // exec-mask region and a wait per element here (52 us of a 112 us kernel).  OWN = 8 covers lists of up to 32 keys (the mean
@@ -543,7 +538,7 @@ __global__ __launch_bounds__(512) void featknn_kernel(const uint4 *__restrict__ 
             __syncthreads();
             const int rq = bq + (t >> 4), part = t & 15, gq = q0 + rq;
             const int M = qcnt[rq];
-            if (gq < N && M <= CAP && !(FK_ABL & 1)) {
+            if (gq < N && M <= CAP) {
                 const fk_u64 *L = Ls + (t >> 4) * CAP;
                 int64_t *dst = idx_out + ((size_t)b * N + gq) * k;
                 constexpr int OWN = CAP / 16;

@@ -575,9 +575,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_conv_kernel(
         __syncthreads();                 // previous chunk's MFMA reads are done
         store_chunk();
         __syncthreads();
-#ifndef PW_PROBE_NO_GLOBAL
         if (k0 + PW_TK < Cin) load_chunk(k0 + PW_TK);     // overlaps with the MFMAs below
-#endif
         // software-pipelined operand fetch: the ds_reads of k-step s+1 are in flight while the four
         // 64-cycle MFMAs of k-step s occupy the matrix pipe (otherwise each k-step exposes one LDS
         // round trip: measured 73 % MFMA-busy before, see profiles/)
@@ -656,9 +654,6 @@ __global__ __launch_bounds__(256, 2) void pointwise_conv_kernel(
                 const int n = n0 + wn * 64 + j * 32 + l31;
                 float v = acc[i][j][e] * sc + sh;
                 if (relu) v = l3d_act(v, relu);
-#ifdef PW_PROBE_NO_STORE
-                if (v == 123.456f)
-#endif
                 if (FULL || n < N) yb[(size_t)co * N + n] = v;
             }
         }

@@ -534,3 +534,34 @@ def test_hot_kernels_compile_without_scratch():
         for k in ks:
             assert k.get(".private_segment_fixed_size", 0) == 0 and k.get(".vgpr_spill_count", 0) == 0, (prefix, k)
             assert k.get(".vgpr_count", 0) <= vgpr_max, (prefix, k.get(".vgpr_count"))
+
+
+def test_every_conditional_region_has_a_driver():
+    """The product build compiles learning3d_amd/csrc with ONE set of flags, so a preprocessor region there is live only through a
+    tool that builds the source with the macro set (a probe that includes it, tools/variant_lab.py, tools/build_variant_lib.py).
+    Every macro in an #if / #ifdef / #elif condition (and in an #ifndef that is not the `#ifndef X / #define X v` default idiom)
+    must be named by a file under tools/: a region nothing can switch on is deleted, not kept (LABLOG R15.1)."""
+    csrc = os.path.join(ROOT, "learning3d_amd", "csrc")
+    used = []                                                 # (file, line, macro)
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hip", ".h")):
+            continue
+        lines = open(os.path.join(csrc, name)).read().split("\n")
+        for i, line in enumerate(lines):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if not m:
+                continue
+            cond = re.sub(r"//.*|/\*.*?\*/", "", m.group(2))
+            macros = set(re.findall(r"\b[A-Za-z_]\w*\b", cond)) - {"defined", "__HIPCC__", "__cplusplus"}
+            if m.group(1) == "ifndef" and i + 1 < len(lines) and re.match(r"\s*#\s*define\s+%s\b" % re.escape(cond.strip()), lines[i + 1]):
+                continue                                      # a default value (or an include guard), not a choice of code
+            used += [(name, i + 1, mac) for mac in sorted(macros)]
+    assert {"CF_TIMING", "CF_TIMELINE", "KS_TIMING"} <= {mac for _, _, mac in used}, "the scan misses conditions that are there"
+    tools_text = ""
+    for d, _, files in os.walk(os.path.join(ROOT, "tools")):
+        for f in sorted(files):
+            if f.endswith((".py", ".hip", ".cpp", ".h", ".inc", ".sh")):
+                tools_text += open(os.path.join(d, f), errors="replace").read() + "\n"
+    named = {mac for mac in {mac for _, _, mac in used} if re.search(r"(?:(?<!\w)|(?<=-D))%s(?!\w)" % re.escape(mac), tools_text)}   # X, or -DX
+    orphans = [f"learning3d_amd/csrc/{name}:{line}: {mac}" for name, line, mac in used if mac not in named]
+    assert not orphans, "conditional regions that no file under tools/ can switch on:\n" + "\n".join(orphans)

@@ -1,5 +1,5 @@
 // Stand-alone timing probe for the two MFMA kernels of mlp.hip (not part of the product).
-// Build variants with -DPW_TK=32, -DPW_PROBE_NO_STORE, -DPW_PROBE_NO_GLOBAL ... and compare.
+// Build variants with -DPW_TK=32 ... and compare.
 #include "../learning3d_amd/csrc/mlp.hip"
 #include "../learning3d_amd/csrc/edgeconv2.hip"
 #include <cstdio>

@@ -1,6 +1,5 @@
-// attention_f16b_kernel at DCP's shape (B=32, H=4, D=128, N=M=1024) stand-alone: microseconds per launch, for ablation builds
-// (-DAB_NOLOAD, -DAB_NOSTAGE, -DAB_NOSOFTMAX, see attention_f16b.hip) that show where its time goes.
-// build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off [-DAF_NOLOAD] [-DAF_NOSPLIT] [-DAF_NOEXP] tools/probe_attention_f16.hip -o tools/bin/probe_att
+// attention_f16b_kernel at DCP's shape (B=32, H=4, D=128, N=M=1024) stand-alone: microseconds per launch, fp32 context and plane image.
+// build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/probe_attention_f16b.hip -o tools/bin/probe_attention_f16b
 #include "../learning3d_amd/csrc/attention_f16b.hip"
 int l3d_attention_absmax3(const float *, const float *, const float *, long, long, long, long, long, int, unsigned *, hipStream_t) { return 0; }
 #include <cstdio>

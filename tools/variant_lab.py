@@ -3,7 +3,7 @@
 small shared library under tools/bin/ (git-ignored; travels to the GPU box), and its entry point is driven with the SAME real
 inputs as the product library's -- outputs compared byte for byte, times interleaved on one box in one process.
 
-    python tools/variant_lab.py build  ef  base=  nostore=-DEF_DIAG_NOSTORE ...      (here: cross-compiles, no GPU)
+    python tools/variant_lab.py build  ef  base=  pd2=-DEF_PD=2 ...              (here: cross-compiles, no GPU)
     python tools/variant_lab.py run    ef  [names...]                                (on the GPU box)
 families: ef = edgeconv_f16b.hip / l3d_edgeconv_forward_f16b (out_mode 2, the bench step's launch)
           cf = conv_f16.hip / l3d_pointwise_conv_f16 (conv5 of the bench step, two planes)
