@@ -19,6 +19,8 @@
 #define CTILE 2048      // candidates per LDS tile, shared by the 4 waves (32 KiB)
 #define CWAVES 4        // waves per workgroup: each scans 1/4 of every tile for the SAME 64*QPL queries
 #define CUNROLL 8
+#define CHAMFER_GRID_MIN 1024    // l3d_chamfer_forward picks chamfer_grid.hip for CHAMFER_GRID_MIN <= min(N, M), max(N, M) <= CHAMFER_GRID_MAX
+#define CHAMFER_GRID_MAX 2048
 #define CHAMFER_LL_BLOCKS 64                                  // l3d_chamfer_loss_local_mb's workgroups
 #define CHAMFER_LL_WS_BYTES (16 + CHAMFER_LL_BLOCKS * 16)
 
@@ -153,7 +155,8 @@ __device__ __forceinline__ void chamfer_loss_tail(double sq, unsigned *__restric
 }
 
 // kernel choice is an ARGUMENT of l3d_chamfer_forward_variant (0 = per-candidate kernels only, 1 = auto, 2 = packed
-// kernel always); there is no process-wide state.  l3d_chamfer_forward == variant 1.
+// kernel always, 3 = chamfer_mfma.hip always, 4 = chamfer_grid.hip always); there is no process-wide state.
+// l3d_chamfer_forward == variant 1.
 
 // ---------------------------------------------------------------------------------------------
 // Packed variant: two queries per lane evaluated with ONE packed-fp32 instruction each step (v_pk_add_f32 /
@@ -311,15 +314,32 @@ __global__ __launch_bounds__(64 * CWAVES) void chamfer_fwd_packed_kernel(const f
 // chamfer_mfma.hip: candidates ranked on the fp16 matrix cores, exact by refinement (same bits out)
 int l3d_chamfer_forward_mfma(const float *xyz1, const float *xyz2, int B, int N, int M, float *dist1, float *dist2,
                              int32_t *idx1, int32_t *idx2, hipStream_t stream);
+// chamfer_grid.hip: candidates sorted into cells in LDS, 27 cells per query, exact by a bound and a fallback scan (same bits out);
+// L3D_ERR_UNSUPPORTED above 2048 points
+int l3d_chamfer_forward_grid(const float *xyz1, const float *xyz2, int B, int N, int M, float *dist1, float *dist2,
+                             int32_t *idx1, int32_t *idx2, hipStream_t stream);
 
 extern "C" int l3d_chamfer_forward_variant(const float *xyz1, const float *xyz2, int B, int N, int M,
                                            float *dist1, float *dist2, int32_t *idx1, int32_t *idx2,
                                            int variant, l3d_stream_t stream)
 {
-    L3D_REQUIRE(xyz1 && xyz2 && dist1 && dist2 && idx1 && idx2 && B > 0 && N > 0 && M > 0 && variant >= 0 && variant <= 3);
+    L3D_REQUIRE(xyz1 && xyz2 && dist1 && dist2 && idx1 && idx2 && B > 0 && N > 0 && M > 0 && variant >= 0 && variant <= 4);
     L3D_REQUIRE(B <= 65535);
     const int l3d_chamfer_forward_mode = variant;
-    const int mx = N > M ? N : M;
+    const int mx = N > M ? N : M, mn = N < M ? N : M;
+    // 1024 ... 2048 points per cloud, at a batch that gives the packed kernel every SIMD a wave (where auto took the packed kernel
+    // before): the grid-pruned search of chamfer_grid.hip.  us per call at B 32, N = M, fastest .. slowest of 7 graph replays of 20
+    // launches on one box (tools/chamfer_bench.py, profiles/round16_chamfer_bench.txt):
+    //      N      packed (variant 2)    grid (variant 4)
+    //    128        4.7 ..  8.5           9.0 ..  9.1
+    //    256        5.7 ..  5.8           8.5 ..  8.6
+    //    512        8.0 ..  8.1           9.2 ..  9.3
+    //   1024       16.9 .. 17.2          11.2 .. 11.3
+    //   2048       50.7 .. 53.6          18.0 .. 18.3
+    // At 512 and below the sort's fixed cost (~4.5 us of dependent LDS round trips) is more than the all-pairs scan it saves.
+    const long grid_wgs2 = (long)l3d_divup(mx, 128) * B * 2;
+    if (variant == 4 || (variant == 1 && mn >= CHAMFER_GRID_MIN && mx <= CHAMFER_GRID_MAX && grid_wgs2 * CWAVES >= 1024))
+        return l3d_chamfer_forward_grid(xyz1, xyz2, B, N, M, dist1, dist2, idx1, idx2, (hipStream_t)stream);
     // large clouds (from 4096 x 4096 pairs per cloud: 81 vs 96 us at B 16, 2.0 vs 4.9 ms at config 4; below that the per-pair kernel
     // wins, profiles/round5_chamfer_bench.txt): the matrix-core ranking + exact refinement; variant 3 forces it, 0 and 2 never use it
     // ... and only with enough workgroups for the part: 2 ceil(max / 512) B of them, each re-scanning every candidate for its bounding
