@@ -1,4 +1,5 @@
-"""ctypes binding of libl3d_hip.so (the C ABI declared in include/*.h: l3d_hip.h and one header per later model).
+"""ctypes binding of libl3d_hip.so (the C ABI declared in include/*.h: l3d_hip.h and one header per later model; models added
+after the table of include/*.h was closed declare theirs in include/models/*.h, read the same way into MODEL_PROTOTYPES).
 
 The headers are the one description of that boundary: the prototypes, the integer #defines and the l3d_status enum are parsed
 from them when this module is imported (SIGNATURES, PROTOTYPES, CONSTANTS), and `call` is the one launch path built on them.
@@ -112,6 +113,17 @@ PROTOTYPES, CONSTANTS = _parse_headers(INCLUDE_DIR)   # name -> Prototype; L3D_*
 globals().update(CONSTANTS)                        # _lib.L3D_OK, _lib.L3D_CONV_F16_TWO_PLANE, _lib.L3D_SELF_ATTN_TQ, ...
 SIGNATURES = {name: [_SCALAR[p.element] if p.indirection == 0 else C.c_void_p for p in proto.params]
               for name, proto in PROTOTYPES.items()}                                                  # name -> argtypes
+# include/models/*.h: the same parser and the same launch path; a name or constant include/*.h already has raises
+MODEL_PROTOTYPES, MODEL_CONSTANTS = _parse_headers(os.path.join(INCLUDE_DIR, "models"))
+for _name in MODEL_PROTOTYPES:
+    if _name in PROTOTYPES:
+        raise L3DError(f"{_name} is declared under include/ and again under include/models/")
+for _name, _value in MODEL_CONSTANTS.items():
+    if _name in CONSTANTS and CONSTANTS[_name] != _value:
+        raise L3DError(f"{_name} is {CONSTANTS[_name]} under include/ and {_value} under include/models/")
+globals().update(MODEL_CONSTANTS)                  # _lib.L3D_RRI_MAX_K, _lib.L3D_GMM_MAX_J
+MODEL_SIGNATURES = {name: [_SCALAR[p.element] if p.indirection == 0 else C.c_void_p for p in proto.params]
+                    for name, proto in MODEL_PROTOTYPES.items()}
 _CALLS = {}                                        # name -> what `call` needs of an entry point; filled by lib()
 
 
@@ -125,9 +137,9 @@ def lib():
                 "(python -m learning3d_amd.build, or __graft_entry__.build()). "
                 "learning3d_amd has no CPU / eager fallback by design.")
         handle = C.CDLL(LIB_PATH)
-        for name, proto in PROTOTYPES.items():
+        for name, proto in (*PROTOTYPES.items(), *MODEL_PROTOTYPES.items()):
             fn = getattr(handle, name)          # AttributeError if the ABI drifted
-            fn.argtypes = SIGNATURES[name]
+            fn.argtypes = SIGNATURES[name] if name in SIGNATURES else MODEL_SIGNATURES[name]
             fn.restype = proto.restype
             # what `call` wants of a tensor passed for each parameter, worked out once: a dtype (pointer to that element type), None
             # (pointer to anything), or that there is none: _POINTERS (a pointer array: ctypes values only), _BY_VALUE
@@ -216,7 +228,7 @@ def f32a(t):
 
 
 def _bad_argument(name, i, a, want):
-    p = PROTOTYPES[name].params[i]
+    p = (PROTOTYPES.get(name) or MODEL_PROTOTYPES[name]).params[i]
     decl = p.ctype + ("" if p.ctype.endswith("*") else " ") + p.name
     if not p.indirection:
         return L3DError(f"{name}: parameter `{decl}` is passed by value, got a tensor")

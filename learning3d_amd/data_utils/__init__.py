@@ -5,3 +5,4 @@ disk_feed:   the reference's on-disk datasets (ModelNet40 h5 -> npz, FlyingThing
 from .device_feed import RegistrationFeed, ResidentRegistrationFeed, uniform_clouds
 from .disk_feed import (ClassificationData, ModelNet40Data, ResidentModelNet40, ResidentSceneflow, SceneflowDataset,
                         load_modelnet40, load_sceneflow_file)
+from .rri import get_rri, rri_features

@@ -9,6 +9,13 @@ import torch
 
 from .._lib import call
 from ..ops.transform_functions import DCPTransform
+from .rri import rri_features
+
+
+def with_rri(cloud, k):
+    """cloud [B,N,3] -> [B,N,3+4k]: DeepGMR's input format, the RRI features of the centred cloud behind the coordinates (reference:
+    data_utils/dataloaders.py:314-317); k None: the cloud itself"""
+    return cloud if k is None else torch.cat([cloud, rri_features(cloud, k, center=True)], dim=2)
 
 
 def uniform_clouds(batch, num_points, lo=0.0, hi=1.0, seed=0, device="cuda"):
@@ -20,11 +27,12 @@ def uniform_clouds(batch, num_points, lo=0.0, hi=1.0, seed=0, device="cuda"):
 
 
 class RegistrationFeed:
-    """Iterator of device batches for DCP-style registration: (template [B,N,3], source [B,N,3], igt [B,4,4])."""
+    """Iterator of device batches for DCP-style registration: (template [B,N,3], source [B,N,3], igt [B,4,4]).
+    rri_neighbors=k: both clouds as [B,N,3+4k], DeepGMR's input (the same clouds and igt as without it)."""
 
     def __init__(self, batch_size, num_points=1024, angle_range=45, translation_range=1, lo=-0.5, hi=0.5, seed=0,
-                 device="cuda", length=None):
-        self.batch_size, self.num_points = batch_size, num_points
+                 device="cuda", length=None, rri_neighbors=None):
+        self.batch_size, self.num_points, self.rri_neighbors = batch_size, num_points, rri_neighbors
         self.lo, self.hi, self.seed, self.device, self.length = lo, hi, seed, torch.device(device), length
         gen = torch.Generator(device=self.device)
         gen.manual_seed(seed)
@@ -41,7 +49,7 @@ class RegistrationFeed:
                                   seed=(self.seed << 20) + self._i, device=self.device)
         source = self.transform(template)
         self._i += 1
-        return template, source, self.transform.igt
+        return with_rri(template, self.rri_neighbors), with_rri(source, self.rri_neighbors), self.transform.igt
 
 
 class ResidentRegistrationFeed:
@@ -52,10 +60,11 @@ class ResidentRegistrationFeed:
 
     data [M,P,3] device tensor (labels [M] optional); `transform` is any of the device transforms of
     ops/transform_functions.py (DCPTransform by default).  Yields (template [B,N,3], source [B,N,3], igt, labels or None);
-    one epoch = every cloud once, in a permutation seeded by (seed, epoch)."""
+    one epoch = every cloud once, in a permutation seeded by (seed, epoch).  rri_neighbors=k: both clouds as [B,N,3+4k],
+    DeepGMR's input (the same clouds and igt as without it)."""
 
     def __init__(self, data, labels=None, batch_size=32, num_points=1024, transform=None, randomize_points=False, seed=0,
-                 drop_last=True):
+                 drop_last=True, rri_neighbors=None):
         if not (data.is_cuda and data.dim() == 3 and data.shape[2] == 3):
             raise ValueError("data must be a device tensor [M, P, 3]")
         if num_points > data.shape[1]:
@@ -63,7 +72,7 @@ class ResidentRegistrationFeed:
         self.data, self.labels = data.float().contiguous(), labels
         self.batch_size, self.num_points, self.randomize_points, self.drop_last = batch_size, num_points, randomize_points, drop_last
         self.gen = torch.Generator(device=data.device)
-        self.seed, self.epoch = seed, 0
+        self.seed, self.epoch, self.rri_neighbors = seed, 0, rri_neighbors
         self.transform = transform if transform is not None else DCPTransform(45, 1, generator=self.gen)
 
     def __len__(self):
@@ -82,4 +91,5 @@ class ResidentRegistrationFeed:
             else:
                 template = self.data[idx, :self.num_points].contiguous()
             source = self.transform(template)
-            yield template, source, self.transform.igt, (self.labels[idx] if self.labels is not None else None)
+            yield (with_rri(template, self.rri_neighbors), with_rri(source, self.rri_neighbors), self.transform.igt,
+                   (self.labels[idx] if self.labels is not None else None))

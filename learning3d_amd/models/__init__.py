@@ -12,3 +12,4 @@ from .curvenet import CurveNet
 from .masknet import MaskNet
 from .segmentation import Segmentation
 from .masknet2 import MaskNet2
+from .deepgmr import DeepGMR
