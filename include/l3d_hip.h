@@ -8,6 +8,12 @@
  *   - caller allocates every output (the reference's dominant convention:
  *     losses/cuda/chamfer_distance/chamfer_distance.py:21-25,
  *     utils/lib/pointnet2_utils.py:25-28,246);
+ *   - memory contract: a `const` pointer is only read.  Every other pointer parameter is an output the call FULLY WRITES --
+ *     every element of the stated shape, whatever the memory held before, and nothing outside it -- unless its comment
+ *     says one of: IN-OUT (read and updated; the comment gives the precondition, e.g. "zeroed by the caller"), or SCRATCH
+ *     (a workspace: contents irrelevant before the call and unspecified after it, no initialisation needed; where a size
+ *     function exists the call stays inside the bytes it returns).  An optional output passed as NULL is skipped.
+ *     tests/golden/memory_contract.py holds this as a table and tests/test_gpu_memory_contract.py checks every entry point;
  *   - `stream` is a hipStream_t passed as void*; launches are asynchronous on it,
  *     there is no internal synchronisation and no global state, so calls are
  *     safe from several host threads (one per device, as nn.DataParallel does);
@@ -46,7 +52,8 @@ const char *l3d_status_string(int status);
 int l3d_last_hip_error(void);
 /* Measurement aid (bench.py): one launch in which every SIMD issues fp16 MFMAs back to back on random operands -- 256 workgroups x
  * 8 waves x 4 * iters instructions of 32 768 FLOP.  The caller times the launch; ticks[0] / ticks[1] * 100 MHz = the shader clock the
- * chip held (the data-sheet peak assumes 2.4 GHz; under this load it holds ~1.5).  sink: 131 072 floats of scratch. */
+ * chip held (the data-sheet peak assumes 2.4 GHz; under this load it holds ~1.5).  sink: 131 072 floats of SCRATCH; ticks [2] is
+ * written (two timer readings: they differ from run to run). */
 int l3d_probe_mfma_sustained(int iters, float *sink, long long *ticks, l3d_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
@@ -65,7 +72,7 @@ int l3d_knn_graph(const float *xyz, int B, int N, int k, int64_t *idx, l3d_strea
  *                    src[b][c][e / div] * (weight ? weight[b][e] : 1)
  * src fp32 [B][C][E/div]; idx int32 [B][E] with values in [0,T); dst fp32 [B][C][T] (fully written).
  * grouping: E = npoint*nsample, div 1;  gather: E = npoint, div 1;  three_interpolate: E = n*3, div 3, weight [B,n,3].
- * workspace: >= l3d_scatter_add_det_workspace_bytes(B,T,E) bytes.  Same inputs -> same bits, every run.
+ * workspace: SCRATCH of >= l3d_scatter_add_det_workspace_bytes(B,T,E) bytes.  Same inputs -> same bits, every run.
  * T * R >= 2^22 (R = 1, 2, 4, 8 placement ranges for E <= 1024, 3072, 7168, more), B*T or B*E >= 2^31, B or C > 65535
  *   -> L3D_ERR_UNSUPPORTED (the Python wrapper splits the targets into windows). */
 size_t l3d_scatter_add_det_workspace_bytes(int B, int T, int E);
@@ -85,7 +92,7 @@ int l3d_edge_gather_max(const float *pq, const int64_t *idx, int B, int Cout, in
 /* knn() of utils/model_common_utils.py:3-9 for FEATURE-space graphs, x [B,C,N], any C (zero-padded to a multiple of 64; PRNet's
  * dynamic DGCNN graphs, models/prnet.py:76-97; C = 3 takes l3d_knn_graph): pd = -xx_j + 2 x_i.x_j - xx_i
  * with the inner product on the matrix cores (bf16x3, fp32-level error) and top-k as the GEMM epilogue, no
- * [B,N,N] tensor.  idx int64 [B,N,k], best first, exact ties -> lower index.  workspace: >=
+ * [B,N,N] tensor.  idx int64 [B,N,k], best first, exact ties -> lower index.  workspace: SCRATCH of >=
  * l3d_knn_feature_workspace_bytes(B,C,N) bytes, 16-byte aligned (holds the split copy of x).
  * k > 64, N > 16384 (N rounded up to 128 past FK_MAXNP), B > 65535 or a misaligned workspace -> L3D_ERR_UNSUPPORTED;
  * k > N -> L3D_ERR_INVALID_ARG. */
@@ -125,8 +132,8 @@ int l3d_chamfer_combine(const double *partials, int world, float *loss, l3d_stre
 /* The same over up to 64 workgroups (the one-workgroup form is a chain of dependent load latencies: 12 us at B=32,
  * N=1024; this one ~4): per-workgroup fp64 partial sums in ws, added in workgroup order by the workgroup that finishes
  * last (deterministic; agrees with l3d_chamfer_loss_local to fp64 rounding of the sum order).  ws:
- * l3d_chamfer_loss_local_ws_bytes() bytes of device memory whose first 8 bytes are zero before the first call (the
- * kernel re-arms them); one ws per stream. */
+ * l3d_chamfer_loss_local_ws_bytes() bytes of device memory whose first 8 bytes are zero before the first call (IN-OUT: the
+ * kernel re-arms them); the rest is SCRATCH; one ws per stream. */
 size_t l3d_chamfer_loss_local_ws_bytes(void);
 int l3d_chamfer_loss_local_mb(const float *dist1, const float *dist2, int B, int N, int M, void *ws, double *partial,
                               float *loss, l3d_stream_t stream);
@@ -134,7 +141,8 @@ int l3d_chamfer_loss_local_mb(const float *dist1, const float *dist2, int B, int
  * (mean sqrt dist1 + mean sqrt dist2) / 2) in ONE launch where the two-queries-per-lane kernel serves the search (N * M < 2^24 pairs
  * per cloud and >= 256 workgroups: configs 2 and 3), else l3d_chamfer_forward + l3d_chamfer_loss_local_mb.  Outputs: dist / idx as
  * l3d_chamfer_forward (bit for bit), partial[4] as l3d_chamfer_partials, loss[0] fp32.  ws: l3d_chamfer_forward_loss_ws_bytes(B, N, M)
- * bytes of device memory, the first 16 zero before the first call (the kernel re-arms them); one ws per stream. */
+ * bytes of device memory, the first 16 zero before the first call (IN-OUT: the kernel re-arms them), the rest SCRATCH; one ws
+ * per stream. */
 size_t l3d_chamfer_forward_loss_ws_bytes(int B, int N, int M);
 int l3d_chamfer_forward_loss(const float *xyz1, const float *xyz2, int B, int N, int M, float *dist1, float *dist2, int32_t *idx1,
                              int32_t *idx2, void *ws, double *partial, float *loss, l3d_stream_t stream);
@@ -146,7 +154,7 @@ int l3d_chamfer_forward_loss(const float *xyz1, const float *xyz2, int B, int N,
 /* ball_query_wrapper(b,n,m,radius,nsample,new_xyz,xyz,idx)   K7 ball_query_gpu.cu:9-45
  *   new_xyz [B,m,3], xyz [B,n,3] -> idx [B,m,nsample] int32; strict d2 < r^2; first hit
  *   back-fills; empty ball = 0 (the callee zero-fills, as pointnet2_utils.py:246 did).
- *   workspace: NULL, or b * (16 n + 16448) bytes of device scratch (16-byte aligned): with it, n >= 2048 and nsample <= 64 the
+ *   workspace: NULL, or b * (16 n + 16448) bytes of device SCRATCH (16-byte aligned, no initialisation): with it, n >= 2048 and nsample <= 64 the
  *   query goes through a per-cloud cell list (a counting sort of the points into cells of edge >= r, then a wave per centroid over
  *   its 27 cells keeping the nsample smallest hit indices) -- the same indices in the same order, ~20x fewer pair evaluations. */
 int l3d_ball_query(int b, int n, int m, float radius, int nsample, const float *new_xyz,
@@ -155,17 +163,20 @@ int l3d_ball_query(int b, int n, int m, float radius, int nsample, const float *
 int l3d_group_points(int b, int c, int n, int npoints, int nsample, const float *points,
                      const int32_t *idx, float *out, l3d_stream_t stream);
 /* group_points_grad_wrapper(b,c,n,npoints,nsample,grad_out,idx,grad_points)   K9 :8-25
- *   grad_points is zero-filled by the callee. */
+ *   grad_points is zero-filled by the callee (fully written).  ORDER-DEPENDENT, like the reference's kernel: an fp32 atomicAdd scatter,
+ *   so a target's sum is formed in an order that differs from run to run and its low bits with it (within the fp32 summation bound);
+ *   l3d_scatter_add_det is the deterministic form and what the Python wrappers call by default.  The same holds for
+ *   l3d_gather_points_grad and l3d_three_interpolate_grad. */
 int l3d_group_points_grad(int b, int c, int n, int npoints, int nsample, const float *grad_out,
                           const int32_t *idx, float *grad_points, l3d_stream_t stream);
 /* gather_points_wrapper(b,c,n,npoints,points,idx,out)   K10 sampling_gpu.cu:8-24 */
 int l3d_gather_points(int b, int c, int n, int npoints, const float *points, const int32_t *idx,
                       float *out, l3d_stream_t stream);
-/* gather_points_grad_wrapper(b,c,n,npoints,grad_out,idx,grad_points)   K11 :46-63 */
+/* gather_points_grad_wrapper(b,c,n,npoints,grad_out,idx,grad_points)   K11 :46-63   (ORDER-DEPENDENT: see l3d_group_points_grad) */
 int l3d_gather_points_grad(int b, int c, int n, int npoints, const float *grad_out,
                            const int32_t *idx, float *grad_points, l3d_stream_t stream);
 /* furthest_point_sampling_wrapper(b,n,m,points,temp,idx)   K12 sampling_gpu.cu:93-209
- *   points [B,n,3]; temp [B,n] scratch (callee initialises it to 1e10); idx [B,m] int32;
+ *   points [B,n,3]; temp [B,n] SCRATCH (no precondition: the callee initialises it to 1e10); idx [B,m] int32;
  *   starts at index 0.  n <= 16384: temp may be NULL (the cloud stays in registers; temp, when given, receives the final
  *   distances); n > 16384: temp is required (NULL -> L3D_ERR_INVALID_ARG); n >= 2^25 -> L3D_ERR_UNSUPPORTED. */
 int l3d_furthest_point_sampling(int b, int n, int m, const float *points, float *temp,
@@ -185,7 +196,7 @@ int l3d_three_interpolate(int b, int c, int m, int n, const float *points, const
  * out fp32 [B, c + c1, n] = [interpolated (c) | skip (c1)]; skip fp32 [B, c1, n] (NULL when c1 == 0). */
 int l3d_three_interpolate_concat(int b, int c, int m, int n, const float *points, const int32_t *idx,
                                  const float *weight, const float *skip, int c1, float *out, l3d_stream_t stream);
-/* three_interpolate_grad_wrapper(b,c,n,m,grad_out,idx,weight,grad_points)   K16 :192-214 */
+/* three_interpolate_grad_wrapper(b,c,n,m,grad_out,idx,weight,grad_points)   K16 :192-214   (ORDER-DEPENDENT: see l3d_group_points_grad) */
 int l3d_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out,
                                const int32_t *idx, const float *weight, float *grad_points,
                                l3d_stream_t stream);
@@ -211,7 +222,7 @@ int l3d_query_ball_point(float radius, int nsample, const float *xyz, const floa
 int l3d_index_points(const float *points, const int64_t *idx, int B, int N, int C, int S,
                      float *out, l3d_stream_t stream);
 /* farthest_point_sample(xyz, npoint) :58-82: start[b] gives the first centroid (the reference
- *   draws it with torch.randint; start == NULL means index 0); temp [B,N] scratch, with the limits of
+ *   draws it with torch.randint; start == NULL means index 0); temp [B,N] SCRATCH (no precondition), with the limits of
  *   l3d_furthest_point_sampling (required for N > 16384). */
 int l3d_farthest_point_sample(const float *xyz, int B, int N, int npoint, const int64_t *start,
                               float *temp, int64_t *centroids, l3d_stream_t stream);
@@ -272,7 +283,7 @@ int l3d_svd3x3_rotation(const float *H, int B, float *R, l3d_stream_t stream);
  *   scores[i][j] = softmax_j( <src_emb[b][:,i], tgt_emb[b][:,j]> * scale ),  scale = 1/sqrt(C) in the reference
  *   src_corr[b][:,i] = sum_j scores[i][j] * tgt[b][:,j]
  * src_emb [B,C,N], tgt_emb [B,C,M], tgt [B,3,M] -> src_corr [B,3,N], all fp32, channel-first (the
- * reference's layouts).  The [B,N,M] score matrix is never materialised.  workspace: scratch of
+ * reference's layouts).  The [B,N,M] score matrix is never materialised.  workspace: SCRATCH of
  * l3d_soft_correspondence_workspace_floats(B,N,M) floats.  C % 16 != 0 -> L3D_ERR_UNSUPPORTED. */
 size_t l3d_soft_correspondence_workspace_floats(int B, int N, int M);
 int l3d_soft_correspondence(const float *src_emb, const float *tgt_emb, const float *tgt, int B, int C, int N,
@@ -285,8 +296,8 @@ int l3d_attention_forward_strided(const float *q, const float *k, const float *v
                                   l3d_stream_t stream);
 /* The same with both GEMMs as f16x2 on the fp16 matrix cores (three fp16 MFMA products per fp32 product instead of bf16x3's
  * six, fp32-level accuracy; attention_f16.hip).  fp16's range is handled inside: one extra pass reads max|q|, max|k|, max|v|
- * into `workspace` (>= 16 bytes of device memory, contents irrelevant) and the operands are scaled by powers of two from
- * them.  Same shapes and strides as l3d_attention_forward_strided.  Output: ctx (fp32, may be NULL) and / or ctx_img, the
+ * into `workspace` (16 bytes of device memory: SCRATCH, contents irrelevant, unless maxima_ready bit 0 makes it an input) and the
+ * operands are scaled by powers of two from them.  Same shapes and strides as l3d_attention_forward_strided.  Output: ctx (fp32, may be NULL) and / or ctx_img, the
  * context as the fp16 activation image of l3d_pointwise_conv_f16 (l3d_f16_image_bytes(1, B N, H D) bytes; may be NULL): the
  * output projection then needs no split pass (|ctx| <= max|v| fixes the plane scale). */
 /* The same with the three operand maxima already in `maxima` (uint32 float bits of upper bounds of max|q|, |k|, |v|, e.g. from
@@ -358,7 +369,8 @@ int l3d_edgeconv_forward_split(const float *xyz, const int64_t *idx, int B, int 
  *               l3d_pointwise_conv_f16 -- conv5 then runs without any split pass
  * Range contract: activations must stay below 16x the expected magnitude (fp16 tops out at 65504); the kernel watches
  * the pooled maxima it forms anyway and stores 1 to *range_flag (device or mapped host memory, may be NULL) when a
- * plane value exceeds 60000 -- the outputs are then invalid and the caller re-runs l3d_edgeconv_forward_split.  k <= 20. */
+ * plane value exceeds 60000 -- the outputs are then invalid and the caller re-runs l3d_edgeconv_forward_split.  k <= 20.
+ * range_flag is IN-OUT for every entry point that takes one: sticky, never cleared by the library; the caller zeroes it. */
 /* The two-plane variant (edgeconv_f16b.hip): same arguments and outputs; two fp16 weight planes per fragment step and an
  * unscaled activation residual (fifth packed copy, csrc/edgeconv_layout.h).  Usable only when the packer could place every
  * layer's weights (packed[l3d_edgeconv_packed_v2_flag_index()] == 1 in the HOST copy of the packed block).
@@ -395,8 +407,8 @@ int l3d_pointwise_conv(const float *x, int x_channel_last, const float *w, const
  *   l3d_split_rows: device fp32 [rows][cols] -> that image (weights: rows = Cout, cols = Cin).
  *   l3d_pointwise_conv_split: x_mode 0 = x [B,Cin,N] fp32, 1 = x [B,N,Cin] fp32,
  *     2 = x already split as l3d_split_rows would split the [B*N][Cin] matrix.
- *     Needs Cout % 256 == 0, N % 128 == 0, Cin % 16 == 0, else L3D_ERR_UNSUPPORTED (callers then use
- *     l3d_pointwise_conv).  Other arguments as l3d_pointwise_conv.
+ *     Needs Cout % 256 == 0, N % 128 == 0 (N % 256 == 0 with pool > 0), Cin % 16 == 0, else L3D_ERR_UNSUPPORTED (callers
+ *     then use l3d_pointwise_conv).  Other arguments as l3d_pointwise_conv.
  * ------------------------------------------------------------------------------------------- */
 size_t l3d_split_bytes(int rows, int cols);
 int l3d_split_rows(const float *src, int rows, int cols, void *dst, l3d_stream_t stream);
@@ -412,10 +424,13 @@ int l3d_pointwise_conv_split(const void *x, int x_mode, const void *w_split, con
  * global -> LDS by DMA with no registers and no VALU.  Range contract: |x| < 65504 (producers raise *range_flag
  * beyond 60000; results are then invalid and the caller falls back to l3d_pointwise_conv_split).
  *   l3d_f16_image_bytes(kind, rows, cols)    kind 0: bytes of one plane; kind 1: of an activation image (h | m' planes + 16
- *                                            bytes: 2^-T, scratch), the activations being stored times 2^T (T per tensor: see
+ *                                            bytes: 2^-T as one float, then 12 bytes of SCRATCH a producer may leave as they
+ *                                            were), the activations being stored times 2^T (T per tensor: see
  *                                            conv_f16.hip); kind 2: of a split weight image of [rows = Cout][cols = Cin]
- *                                            (H | Hs | M planes + 16 bytes of maxima + 2^-S_r per row r: one exponent per row)
- *   l3d_conv_f16_split_weights               w [Cout][Cin] fp32 (device) -> that image (device); two small launches
+ *                                            (H | Hs | M planes + 16 bytes of maxima + 2^-S_r per row r: one exponent per row,
+ *                                            the list padded to a multiple of 16 bytes (the padding is SCRATCH))
+ *   l3d_conv_f16_split_weights               w [Cout][Cin] fp32 (device) -> that image (device), every byte up to the padding
+ *                                            written; two small launches
  *   l3d_split_f16_rows                       x [rows][C] fp32, or [B][C][Npts] with channel_first -> activation image
  *   l3d_pointwise_conv_f16                   y[b][co][n] = act(scale[co] sum_k w[co][k] x[b][n][k] + shift[(b,)co]);
  *                                            Cin % 16 == 0 and (Cout % 256 == 0, N % 256 == 0) or (Cout % 128 == 0,
@@ -444,7 +459,7 @@ int l3d_split_f16_rows(const float *x, long rows, int C, int channel_first, int 
  *             channel finishes it), pool = K for the max over a group's K neighbours (models/flownet3d.py:179, :234); the
  *             layer's [B,Cout,N] output is then never written
  *   amax_out  with y: max|y| per group of amax_cdiv output channels (amax_cdiv % 256 == 0) into amax_out[Cout / amax_cdiv]
- *             (uint32 float bits, atomic maximum: the caller zeroes them first): the operand maxima
+ *             (uint32 float bits, atomic maximum: IN-OUT, the caller zeroes them first): the operand maxima
  *             l3d_attention_forward_f16b wants, from the projection's own epilogue (utils/transformer.py:183-189)
  * flags     L3D_CONV_F16_TWO_PLANE: the input image's residual plane is UNSCALED (m = f16(X - h); written by
  *           l3d_edgeconv_forward_f16b with out_mode 2, by l3d_layernorm_planes_cf / l3d_attention_forward_f16b / this function when
@@ -463,8 +478,9 @@ int l3d_pointwise_conv_f16(const void *x_planes, const void *w_planes, const flo
 /* One operand of a training-path product on the f16x2 kernel (an nn.Linear over rows, utils/transformer.py:183-189 of the reference, and
  * its dgrad): x [rows][C] fp32 with row stride `row_stride` -> fp16 planes h | m of x 2^T, UNSCALED residual; T from the window's maximum
  * (kind 0) or from each row's own maximum (kind 1: the image's per-row exponents).
- * kind 0: an activation image (l3d_f16_image_bytes(1, rows, C)); kind 1: the two planes in the slots of a weight image
- * (l3d_f16_image_bytes(2, rows, C)), i.e. the w_planes operand of l3d_pointwise_conv_f16 with L3D_CONV_F16_TWO_PLANE.  With the batch's
+ * kind 0: an activation image (l3d_f16_image_bytes(1, rows, C)); kind 1: the two planes in the H and M slots of a weight image
+ * (l3d_f16_image_bytes(2, rows, C); its Hs slot, the second plane, is NOT written: SCRATCH the two-plane form never reads), i.e. the
+ * w_planes operand of l3d_pointwise_conv_f16 with L3D_CONV_F16_TWO_PLANE.  With the batch's
  * rows as w_planes (kind 1), the layer's [Cout][Cin] matrix as x_planes (kind 0), B = 1, "Cout" = rows, "N" = Cout and
  * L3D_CONV_F16_SHIFT_N the kernel's output is y [rows][Cout] = x W^T + b, row-major.  rows % 256 == 0 and Cout % 256 == 0 for the GEMM. */
 int l3d_split_f16_operand(const float *x, long rows, int C, long row_stride, int kind, void *dst, int *range_flag, l3d_stream_t stream);
@@ -491,7 +507,7 @@ int l3d_fold_mlp_f16(const float *g, int CG, const float *w5g, const float *s5, 
  * Approximate EMD  == losses/cuda/emd_torch/pkg/include/emd.h:47-50 (pybind `_emd_ext._emd`)
  *   emd_forward(xyz1,xyz2) -> cost [B], match [B,n,m] (indexed [l*n+k], emd.cuh:158); the reference's forward allocates its
  *   own scratch (pkg/src/cuda/emd.cu:18-22) -- here the caller passes `workspace` of l3d_emd_workspace_bytes(B,n,m) bytes
- *   (the ten levels' ratioL / ratioR, the remainders and the cost partials; no initialisation needed).  22 stream-ordered
+ *   (SCRATCH: the ten levels' ratioL / ratioR, the remainders and the cost partials; no initialisation needed).  22 stream-ordered
  *   launches, no host synchronisation.   emd_backward(xyz1,xyz2,match) -> grad1, grad2.
  *   split: lanes per row in the sweeps, 1, 2 or 4; 0 = chosen from B * min(n, m).  The result's bits do not depend on it.
  * ------------------------------------------------------------------------------------------- */
@@ -568,8 +584,8 @@ int l3d_bn_act_backward(const float *dy, const float *z, const float *scale, con
 int l3d_sum_clouds_f64(const double *part, int B, long M, double *tot, l3d_stream_t stream);
 /* Per-channel finalisation of a layer's statistics in ONE launch each way (models/_train.py did it with ~25 + ~8 scalar-sized torch
  * operations per layer).  Forward, mode 0 = train-mode BatchNorm from the per-cloud sums part [B][C][2] of the conv output without
- * its bias (clouds added in cloud order, fp64), running statistics updated as torch.nn.BatchNorm does when given; 1 = eval-mode
- * BatchNorm (running statistics); 2 = no BatchNorm.  -> mean64, rstd64, gr64 = gamma rstd (fp64), scale, shift (fp32):
+ * its bias (clouds added in cloud order, fp64), running statistics updated as torch.nn.BatchNorm does when given (IN-OUT); 1 = eval-mode
+ * BatchNorm (running statistics: read, left as they are); 2 = no BatchNorm.  -> mean64, rstd64, gr64 = gamma rstd (fp64), scale, shift (fp32):
  * y = act(z scale + shift).  Backward: per-cloud (sum g, sum g zhat) of this rank (part_local) and of all ranks (part_all, NULL =
  * the same) -> the batch means m1, m2 (zeros without batch statistics) and this shard's dbias / dgamma / dbeta (each may be NULL). */
 int l3d_bn_finalize(const double *part, int B, int C, double n, const float *bias, const float *gamma, const float *beta, double eps,
@@ -586,7 +602,7 @@ int l3d_max_last_backward(const float *g, const unsigned char *idx, long R, int 
 
 /* Backward of the pointer network's LayerNorm (utils/transformer.py:109-119: unbiased std, eps added to std; forward =
  * l3d_layernorm_planes): x, g = dL/dy, dx [rows][C]; a [C]; da, db [C] summed over the rows in a fixed order (workgroup partials in
- * the workspace, then fp64 in workgroup order).  workspace: l3d_layernorm_backward_workspace_floats(rows, C) floats.
+ * the workspace, then fp64 in workgroup order).  workspace: SCRATCH of l3d_layernorm_backward_workspace_floats(rows, C) floats.
  * C % 4 == 0, C <= 2048, 16-byte aligned pointers. */
 size_t l3d_layernorm_backward_workspace_floats(long rows, int C);
 int l3d_layernorm_ref_backward(const float *x, const float *a, const float *g, float eps, long rows, int C, float *dx,
@@ -611,12 +627,13 @@ int l3d_sa_mlp3_fused(const float *xyz, const float *new_xyz, const float *feat,
  * read where the tensors lie (a transposed operand is its strides swapped).
  *   C[i][j] = act(alpha A[i][j] B[i][j] + bias) (+ C[i][j]),  A [M x K], B [K x N], C [M x N], i < nb1, j < nb2
  *   *_strides: four element strides {batch1, batch2, row, column} (host arrays); flags: 1 accumulate into C, 2 ReLU, 4 bias[n],
- *   8 bias[m]; parts > 1: K split into `parts` ranges through `workspace` (nb1 nb2 parts M N floats), summed in ascending order
+ *   8 bias[m] (C is IN-OUT with flag 1, fully written without it); parts > 1: K split into `parts` ranges through `workspace`
+ *   (SCRATCH of nb1 nb2 parts M N floats; NULL with parts <= 1), summed in ascending order
  *   (weight gradients: few output tiles, K = every row of the batch).  fp32 MFMA: an exact fma chain per element, ascending k.
  * l3d_softmax_rows: dp == NULL: y = softmax(scale x) over the last axis of [rows][cols]; dp given: y = scale p (dp - sum_j p_j dp_j)
  * with p = x (the backward through the softmax and the score scale).  y may alias x / dp.  cols <= 8192.
  * l3d_colsum_rows: out[c] = sum_r x[r row_stride + c] -- the bias gradient of an nn.Linear over rows (db = 1^T g); a fixed summation
- * tree over chunks of 128 rows: the same bits on every run (workspace: l3d_colsum_rows_workspace_bytes). */
+ * tree over chunks of 128 rows: the same bits on every run (workspace: SCRATCH of l3d_colsum_rows_workspace_bytes(rows, cols) bytes). */
 int l3d_bmm_f32(const float *A, const long *a_strides, const float *B, const long *b_strides, float *C, const long *c_strides,
                 int nb1, int nb2, int M, int N, int K, float alpha, int flags, const float *bias, int parts, float *workspace,
                 l3d_stream_t stream);
@@ -630,7 +647,7 @@ int l3d_colsum_rows(const float *x, long rows, int cols, long row_stride, void *
  *   dw[co][ci] = sum_b sum_p dz[b][co][p] x[b][ci][p]          dz [B,Cout,P], x [B,Cin,P] fp32
  * exact-fp32 products on the fp32 MFMA, the B*P reduction split into (cloud, pc-point chunk) pieces whose partial sums
  * are added in piece order in fp64: deterministic (no atomics) and accurate to one rounding of <= pc-term fp32 sums.
- * pc <= 0: 2048.  workspace: l3d_wgrad_workspace_bytes(B, Cout, Cin, P, pc) bytes, caller-allocated.
+ * pc <= 0: 2048.  workspace: SCRATCH of l3d_wgrad_workspace_bytes(B, Cout, Cin, P, pc) bytes, caller-allocated.
  * ------------------------------------------------------------------------------------------- */
 size_t l3d_wgrad_workspace_bytes(int B, int Cout, int Cin, long P, int pc);
 int l3d_wgrad(const float *dz, const float *x, int B, int Cout, int Cin, long P, int pc, float *workspace, float *dw,

@@ -31,7 +31,7 @@ int l3d_chamfer_forward_variant(const float *xyz1, const float *xyz2, int B, int
  *                                      int32_t *idx1, int32_t *idx2, int32_t *stats, l3d_stream_t stream)
  * stats[0] += queries whose answer the bound accepted, stats[1] += queries sent to the fallback list, stats[2] += workgroups that
  * took the exact scan as a whole (a non-finite coordinate, or an extent of zero / outside the bound's range).  stats: 3 int32 on
- * the device, zeroed by the caller.  Same outputs as variant 4. */
+ * the device, IN-OUT, zeroed by the caller.  Same outputs as variant 4. */
 
 /* The same with the kernel choice as an argument (bit-identical results: both add a point's terms in the order of
  * chamfer_distance.cpp:138-176): variant 0 = scan of the partner cloud's selections per point, 2 = selections sorted by

@@ -25,7 +25,7 @@ int l3d_mask_tail(const float *x, const float *w4, const float *b4, const float 
  *          rank(i) = #{j : m_j > m_i, or m_j == m_i and j < i}; a NaN orders above every number and equal to another NaN; -0 == +0.
  *          Exactly k points per cloud (k <= N).  idx int64 [B,k], out [B,k,3].
  *   k == 0 (mask > threshold of a single pair, B == 1): selected iff m_i > threshold (never a NaN).  idx int64 [1,N] and out [1,N,3],
- *          of which the first count[0] entries are written.
+ *          of which the first count[0] entries are written (the rest is left as it was).
  * In both modes the selected indices are written in ascending order, out[b,s,:] = points[b, idx[b,s], :], count int32 [B] = the
  * number selected.  N <= 16384 (a cloud's keys live in one workgroup's LDS), else L3D_ERR_UNSUPPORTED; k < 0, k > N, or k == 0 with
  * B != 1 -> L3D_ERR_INVALID_ARG. */

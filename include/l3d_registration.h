@@ -22,7 +22,7 @@ int l3d_reg_pose_first_layer(const float *cloud, const float *T, const float *dt
 
 /* Finite-difference Jacobian -> pseudo-inverse (approx_Jic + compute_inverse_jacobian, models/pointnetlk.py:109-152), one
  * workgroup per cloud: J[c][k] = (f0[c] - f[k][c]) / dt[k], H = J^T J and H^-1 (Gauss-Jordan, partial pivoting) in fp64,
- * pinv [B,6,K] = H^-1 J^T rounded to fp32 once.  f0 [B,K], f [B,6,K], dt [6].  singular: int32 [1 + B], zeroed by the caller;
+ * pinv [B,6,K] = H^-1 J^T rounded to fp32 once.  f0 [B,K], f [B,6,K], dt [6].  singular: int32 [1 + B], IN-OUT, zeroed by the caller;
  * an exactly zero pivot sets singular[1 + b] and singular[0] (and that cloud's pinv to 0) where torch.inverse raises. */
 int l3d_reg_jac_pinv(const float *f0, const float *f, const float *dt, int B, int K, float *pinv, int32_t *singular,
                      l3d_stream_t stream);
@@ -32,15 +32,17 @@ int l3d_reg_jac_pinv(const float *f0, const float *f, const float *dt, int B, in
  *   est_T_series[step + 1] <- est_T.
  * Launch 0 takes est_T = identity and writes est_T_series[0] itself; once done is set (or singular[0] is), a launch leaves est_T, r
  * and the counter as they are and only fills its slot of est_T_series (nothing at all when singular).
- * state: int32 [4] = {done, iterations begun, stopped in iteration 0, ticket}, zeroed by the caller once (the ticket returns
- * to 0 after every launch); ws: fp32 [B,8] scratch; est_T [B,4,4]; series [maxiter + 1,B,4,4]; r [B,K]. */
+ * state: int32 [4] = {done, iterations begun, stopped in iteration 0, ticket}, IN-OUT, zeroed by the caller once (the ticket returns
+ * to 0 after every launch); ws: fp32 [B,8] SCRATCH; est_T [B,4,4], series [maxiter + 1,B,4,4] and r [B,K] are IN-OUT: state the
+ * launches of one loop hand on (launch 0 reads none of them). */
 int l3d_reg_iclk_step(const float *f, const float *f0, const float *pinv, int B, int K, int step, int maxiter, float xtol,
                       const int32_t *singular, float *ws, int32_t *state, float *est_T, float *series, float *r,
                       l3d_stream_t stream);
 
 /* iPCRNet's pose update (models/pcrnet.py:33-50): pose7 [B,7] = the head's output (quaternion w x y z, translation) ->
  * q normalised (eps 1e-12), est_R <- R_q est_R [B,3,3], est_t <- R_q est_t + t_q [B,3], est_T [B,4,4] = [est_R est_t; 0 0 0 1].
- * first != 0: the incoming pose is the identity and est_R / est_t are not read.  fp64 inside, rounded to fp32 once. */
+ * est_R / est_t are IN-OUT; first != 0: the incoming pose is the identity and est_R / est_t are not read (then fully written).  fp64
+ * inside, rounded to fp32 once. */
 int l3d_reg_quat_update(const float *pose7, int B, int first, float *est_R, float *est_t, float *est_T, l3d_stream_t stream);
 
 #ifdef __cplusplus

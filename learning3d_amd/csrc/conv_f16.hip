@@ -722,7 +722,9 @@ extern "C" int l3d_conv_f16_split_weights(const float *w, int Cout, int Cin, voi
     unsigned char *d = (unsigned char *)dst;
     unsigned *amax = (unsigned *)(d + 3 * pb + 4);
     float *rinv = (float *)(d + 3 * pb + 16);
-    if (hipMemsetAsync(amax, 0, 8, st) != hipSuccess) return L3D_ERR_LAUNCH;       // (unused) and row-sum maximum
+    // the image's 16 bytes behind the planes: (unused) | (unused) | row-sum maximum | (unused).  All four are zeroed: the header
+    // promises a fully written image, and the two outer words were left as the allocation held them (nothing reads them)
+    if (hipMemsetAsync(d + 3 * pb, 0, 16, st) != hipSuccess) return L3D_ERR_LAUNCH;
     hipLaunchKernelGGL(cf_rowsum_kernel, dim3((unsigned)l3d_divup(Cout, 4)), dim3(256), 0, st, w, Cout, Cin, amax + 1, rinv);
     const long cells = (long)Cout * ((Cin + 7) / 8);
     hipLaunchKernelGGL(cf_split_w_kernel, dim3((unsigned)l3d_divup(cells, 256)), dim3(256), 0, st, w, Cout, Cin, (const float *)rinv,
