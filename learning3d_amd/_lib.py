@@ -1,5 +1,7 @@
 """ctypes binding of libl3d_hip.so (the C ABI declared in include/*.h: l3d_hip.h and one header per later model; models added
 after the table of include/*.h was closed declare theirs in include/models/*.h, read the same way into MODEL_PROTOTYPES).
+Both of those tables are pinned by tests.  include/ext/*.h is the third and the OPEN one (EXT_PROTOTYPES, EXT_SIGNATURES,
+EXT_CONSTANTS): a new model adds its header there, and nothing pins that table's size or contents.
 
 The headers are the one description of that boundary: the prototypes, the integer #defines and the l3d_status enum are parsed
 from them when this module is imported (SIGNATURES, PROTOTYPES, CONSTANTS), and `call` is the one launch path built on them.
@@ -124,6 +126,28 @@ for _name, _value in MODEL_CONSTANTS.items():
 globals().update(MODEL_CONSTANTS)                  # _lib.L3D_RRI_MAX_K, _lib.L3D_GMM_MAX_J
 MODEL_SIGNATURES = {name: [_SCALAR[p.element] if p.indirection == 0 else C.c_void_p for p in proto.params]
                     for name, proto in MODEL_PROTOTYPES.items()}
+# include/ext/*.h: the open table (RPMNet and later models); a name or constant that either earlier table has raises
+EXT_PROTOTYPES, EXT_CONSTANTS = _parse_headers(os.path.join(INCLUDE_DIR, "ext"))
+for _name in EXT_PROTOTYPES:
+    if _name in PROTOTYPES or _name in MODEL_PROTOTYPES:
+        raise L3DError(f"{_name} is declared under include/ext/ and again in an earlier header table")
+for _name, _value in EXT_CONSTANTS.items():
+    if _name in CONSTANTS or _name in MODEL_CONSTANTS:
+        raise L3DError(f"{_name} is defined under include/ext/ and again in an earlier header table")
+globals().update(EXT_CONSTANTS)                    # _lib.L3D_PPF_MAX_K, _lib.L3D_GN_CONV_MAX_COUT, ...
+EXT_SIGNATURES = {name: [_SCALAR[p.element] if p.indirection == 0 else C.c_void_p for p in proto.params]
+                  for name, proto in EXT_PROTOTYPES.items()}
+_TABLES = ((PROTOTYPES, SIGNATURES), (MODEL_PROTOTYPES, MODEL_SIGNATURES), (EXT_PROTOTYPES, EXT_SIGNATURES))
+
+
+def _declared(name):
+    """-> (Prototype, argtypes) of an entry point, from whichever header table declares it"""
+    for protos, sigs in _TABLES:
+        if name in protos:
+            return protos[name], sigs[name]
+    raise L3DError(f"{name} is declared by no header")
+
+
 _CALLS = {}                                        # name -> what `call` needs of an entry point; filled by lib()
 
 
@@ -137,9 +161,10 @@ def lib():
                 "(python -m learning3d_amd.build, or __graft_entry__.build()). "
                 "learning3d_amd has no CPU / eager fallback by design.")
         handle = C.CDLL(LIB_PATH)
-        for name, proto in (*PROTOTYPES.items(), *MODEL_PROTOTYPES.items()):
+        for name in [n for protos, _ in _TABLES for n in protos]:
+            proto, argtypes = _declared(name)
             fn = getattr(handle, name)          # AttributeError if the ABI drifted
-            fn.argtypes = SIGNATURES[name] if name in SIGNATURES else MODEL_SIGNATURES[name]
+            fn.argtypes = argtypes
             fn.restype = proto.restype
             # what `call` wants of a tensor passed for each parameter, worked out once: a dtype (pointer to that element type), None
             # (pointer to anything), or that there is none: _POINTERS (a pointer array: ctypes values only), _BY_VALUE
@@ -228,7 +253,7 @@ def f32a(t):
 
 
 def _bad_argument(name, i, a, want):
-    p = (PROTOTYPES.get(name) or MODEL_PROTOTYPES[name]).params[i]
+    p = _declared(name)[0].params[i]
     decl = p.ctype + ("" if p.ctype.endswith("*") else " ") + p.name
     if not p.indirection:
         return L3DError(f"{name}: parameter `{decl}` is passed by value, got a tensor")

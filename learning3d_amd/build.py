@@ -29,7 +29,7 @@ def _stale(target, deps):
 def build(force=False, verbose=False):
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
     hdrs = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(HERE, "..", "include", "*.h")) + \
-        glob.glob(os.path.join(HERE, "..", "include", "models", "*.h"))
+        glob.glob(os.path.join(HERE, "..", "include", "models", "*.h")) + glob.glob(os.path.join(HERE, "..", "include", "ext", "*.h"))
     objdir = os.path.join(CSRC, "build")
     os.makedirs(objdir, exist_ok=True)
 

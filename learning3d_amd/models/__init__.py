@@ -13,3 +13,5 @@ from .masknet import MaskNet
 from .segmentation import Segmentation
 from .masknet2 import MaskNet2
 from .deepgmr import DeepGMR
+from .ppfnet import PPFNet
+from .rpmnet import RPMNet

@@ -1,0 +1,294 @@
+"""Drop-in for learning3d/models/rpmnet.py on MI355X: RPMNet, iterative registration by soft correspondences.  Per iteration a
+small PointNet predicts the annealing parameters beta and alpha from both clouds, PPFNet gives a unit feature per point, the
+feature distances become a [B,J,K] affinity -beta (dist - alpha), a Sinkhorn normalisation with a slack row and column turns it
+into a soft permutation, and a weighted Kabsch step gives the transform (reference: models/rpmnet.py; examples/test_rpmnet.py).
+ParameterPredictionNet, to_numpy, se3_transform, match_features, sinkhorn, compute_rigid_transform and RPMNet keep the
+reference's names, arguments, attributes (add_slack, num_sk_iter; after a forward beta, alpha, feat_source, feat_template,
+affinity, perm_matrix), result keys and state_dict keys (weights_net.*, feat_extractor.*), so its checkpoints load with strict=True.
+
+Deliberate differences:
+  * RPMNet(feature_model=None) builds its own PPFNet.  The reference's default argument is ONE PPFNet instance made at import and
+    shared by every default-constructed RPMNet; here two models never share weights by accident (as MaskNet's default does).
+  * On the fused route the assertion on det(R) > 0 is dropped: it is a host read in the middle of the loop, and the kernel picks
+    the rotation by the determinant's sign itself.
+  * beta and alpha of every iteration are gathered on the device and become numpy once, after the last launch; the reference
+    copies them to the host inside every iteration.
+  * split_normals builds the zero normals of a [B,N,3] cloud in the cloud's own dtype (zeros_like): fp64 clouds without normals
+    work; the reference builds fp32 zeros and fails there.
+
+Two routes:
+  * the op sequence: the reference's torch ops; CPU tensors, fp64 (`net.double()`) and autograd work.  It also serves
+    add_slack=False, a Sinkhorn eps > 0, metric='angle', and any feature network without a `fused_features` the kernels take.
+  * fused (FUSED, device fp32, nothing to differentiate, add_slack, a fusable PPFNet): RPMNet._forward_fused.  The template's
+    features are computed once and reused by the later iterations (GroupNorm has no running state: the same bits); per iteration
+    the parameter network in torch, PPFNet.fused_features of the moved source, the affinity from utils.square_distance,
+    l3d_sinkhorn_slack (potentials only, the padded matrix is never written; it also gives the row sums and the weighted template
+    points) and l3d_rigid_transform_weighted (3x3 SVD on the device).  No host read inside the loop.
+ParameterPredictionNet's [B,1024,J+K] stack stays in torch on both routes.
+_lib.LAUNCH_LOG shows the route: l3d_ppf_group and l3d_gn_conv appear on the fused one only (the public sinkhorn takes
+l3d_sinkhorn_slack on device fp32 tensors without autograd on either route, unless FUSED is off)."""
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import _lib
+from .._lib import call, f32c, on_device_of
+from ..utils import angle_difference, square_distance as _device_square_distance
+from .ppfnet import PPFNet, _device_ops_take, _square_distance
+from . import _fused
+
+_EPS = 1e-5  # To prevent division by zero
+FUSED = True                 # False: the op sequence for every input (A/B: tools/rpmnet_bench.py)
+
+
+def _block(layer, groups, width):
+    return [layer, nn.GroupNorm(groups, width), nn.ReLU()]
+
+
+class ParameterPredictionNet(nn.Module):
+    """PointNet over both clouds (a fourth coordinate tells them apart) -> beta, alpha > 0 per pair"""
+
+    def __init__(self, weights_dim):
+        super().__init__()
+        self.weights_dim = weights_dim
+        pre, cin = [], 4
+        for cout, groups in ((64, 8), (64, 8), (64, 8), (128, 8), (1024, 16)):
+            pre += _block(nn.Conv1d(cin, cout, 1), groups, cout)
+            cin = cout
+        self.prepool = nn.Sequential(*pre)
+        self.pooling = nn.AdaptiveMaxPool1d(1)
+        self.postpool = nn.Sequential(*_block(nn.Linear(1024, 512), 16, 512), *_block(nn.Linear(512, 256), 16, 256),
+                                      nn.Linear(256, 2 + int(np.prod(weights_dim))))
+
+    def forward(self, x):
+        """x = [src [B,J,3], ref [B,K,3]] -> beta [B], alpha [B]"""
+        src = F.pad(x[0], (0, 1), mode='constant', value=0)
+        ref = F.pad(x[1], (0, 1), mode='constant', value=1)
+        feat = self.prepool(torch.cat([src, ref], dim=1).permute(0, 2, 1))
+        raw = self.postpool(torch.flatten(self.pooling(feat), start_dim=-2))
+        return F.softplus(raw[:, 0]), F.softplus(raw[:, 1])
+
+
+def to_numpy(tensor):
+    """a tensor's values as a numpy array (an array passes through)"""
+    if isinstance(tensor, torch.Tensor):
+        return tensor.detach().cpu().numpy()
+    if isinstance(tensor, np.ndarray):
+        return tensor
+    raise NotImplementedError
+
+
+def se3_transform(g, a, normals=None):
+    """g [B,3|4,4], a [B,N,3] -> R a + t; with normals [B,N,3] also the rotated normals"""
+    R, p = g[..., :3, :3], g[..., :3, 3]
+    if g.dim() != a.dim():
+        raise NotImplementedError
+    b = torch.matmul(a, R.transpose(-1, -2)) + p[..., None, :]
+    if normals is None:
+        return b
+    return b, normals @ R.transpose(-1, -2)
+
+
+def _pairwise_sq(src, dst):
+    if _device_ops_take(src, dst):
+        return _device_square_distance(src, dst)
+    return _square_distance(src, dst)
+
+
+def match_features(feat_src, feat_ref, metric='l2'):
+    """feat_src [B,J,C], feat_ref [B,K,C] -> [B,J,K]: squared distances ('l2') or angles ('angle')"""
+    assert feat_src.shape[-1] == feat_ref.shape[-1]
+    if metric == 'l2':
+        return _pairwise_sq(feat_src, feat_ref)
+    if metric == 'angle':
+        s = feat_src / (torch.norm(feat_src, dim=-1, keepdim=True) + _EPS)
+        r = feat_ref / (torch.norm(feat_ref, dim=-1, keepdim=True) + _EPS)
+        return angle_difference(s, r)
+    raise NotImplementedError
+
+
+def sinkhorn_slack(log_alpha, n_iters, xyz_ref=None, eps=_EPS, want_log=True, want_perm=False):
+    """l3d_sinkhorn_slack on device fp32 log_alpha [B,J,K] -> (log_perm, perm, rowsum [B,J], weighted [B,J,3]); the outputs that
+    were not asked for are None (rowsum and weighted come with xyz_ref [B,K,3])"""
+    A = f32c(log_alpha)
+    B, J, K = A.shape
+    dev = A.device
+    log_perm = torch.empty_like(A) if want_log else None
+    perm = torch.empty_like(A) if want_perm else None
+    rowsum = weighted = None
+    if xyz_ref is not None:
+        xyz_ref = f32c(xyz_ref)
+        rowsum = torch.empty((B, J), dtype=torch.float32, device=dev)
+        weighted = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
+    ws = torch.empty(_lib.lib().l3d_sinkhorn_workspace_bytes(B, J, K) // 8, dtype=torch.float64, device=dev)
+    call("l3d_sinkhorn_slack", A, B, J, K, int(n_iters), xyz_ref, float(eps), log_perm, perm, rowsum, weighted, ws)
+    return log_perm, perm, rowsum, weighted
+
+
+def sinkhorn(log_alpha, n_iters: int = 5, slack: bool = True, eps: float = -1) -> torch.Tensor:
+    """n_iters rounds of row then column normalisation of exp(log_alpha) [B,J,K] in the log domain -> log of the result.  slack:
+    an extra row and column of zeros take part and are never normalised themselves, so rows and columns sum to <= 1.  eps > 0:
+    stop once the matrix moves by less than eps (summed absolute change, the largest over the batch).
+    Device fp32 without autograd, slack and eps <= 0: l3d_sinkhorn_slack.  Anything else: torch."""
+    if slack and eps <= 0 and _device_ops_take(log_alpha) and FUSED:
+        with on_device_of(log_alpha):
+            return sinkhorn_slack(log_alpha, n_iters)[0]
+    prev = None
+    if slack:
+        padded = F.pad(log_alpha, (0, 1, 0, 1))
+        for _ in range(n_iters):
+            padded = torch.cat((padded[:, :-1, :] - torch.logsumexp(padded[:, :-1, :], dim=2, keepdim=True),
+                                padded[:, -1:, :]), dim=1)                       # every row but the slack row
+            padded = torch.cat((padded[:, :, :-1] - torch.logsumexp(padded[:, :, :-1], dim=1, keepdim=True),
+                                padded[:, :, -1:]), dim=2)                       # every column but the slack column
+            if eps > 0:
+                now = torch.exp(padded[:, :-1, :-1])
+                if prev is not None and torch.max(torch.sum(torch.abs(now - prev), dim=[1, 2])) < eps:
+                    break
+                prev = now.clone()
+        return padded[:, :-1, :-1]
+    for _ in range(n_iters):
+        log_alpha = log_alpha - torch.logsumexp(log_alpha, dim=2, keepdim=True)
+        log_alpha = log_alpha - torch.logsumexp(log_alpha, dim=1, keepdim=True)
+        if eps > 0:
+            now = torch.exp(log_alpha)
+            if prev is not None and torch.max(torch.sum(torch.abs(now - prev), dim=[1, 2])) < eps:
+                break
+            prev = now.clone()
+    return log_alpha
+
+
+def rigid_transform_weighted(a, b, weights):
+    """l3d_rigid_transform_weighted: a, b [B,M,3], weights [B,M] (device fp32) -> T [B,3,4]"""
+    a, b, weights = f32c(a), f32c(b), f32c(weights)
+    B, M, _ = a.shape
+    T = torch.empty((B, 3, 4), dtype=torch.float32, device=a.device)
+    call("l3d_rigid_transform_weighted", a, b, weights, B, M, _EPS, T)
+    return T
+
+
+def compute_rigid_transform(a: torch.Tensor, b: torch.Tensor, weights: torch.Tensor):
+    """the op-sequence weighted Kabsch: a, b [B,M,3], weights [B,M] -> T [B,3,4] with T a = b.  Differentiable through torch.svd."""
+    wn = weights[..., None] / (torch.sum(weights[..., None], dim=1, keepdim=True) + _EPS)
+    ca = torch.sum(a * wn, dim=1)
+    cb = torch.sum(b * wn, dim=1)
+    cov = (a - ca[:, None, :]).transpose(-2, -1) @ ((b - cb[:, None, :]) * wn)
+    u, _, v = torch.svd(cov, some=False, compute_uv=True)
+    rot_pos = v @ u.transpose(-1, -2)
+    v_neg = v.clone()
+    v_neg[:, :, 2] *= -1                                                        # the smallest singular direction flipped
+    rot_neg = v_neg @ u.transpose(-1, -2)
+    rot = torch.where(torch.det(rot_pos)[:, None, None] > 0, rot_pos, rot_neg)
+    assert torch.all(torch.det(rot) > 0)
+    t = cb[:, :, None] - rot @ ca[:, :, None]
+    return torch.cat((rot, t), dim=2)
+
+
+class RPMNet(nn.Module):
+    def __init__(self, feature_model=None):
+        super().__init__()
+        self.add_slack = True
+        self.num_sk_iter = 5
+        self.weights_net = ParameterPredictionNet(weights_dim=[0])
+        self.feat_extractor = feature_model if feature_model is not None else PPFNet()
+
+    def compute_affinity(self, beta, feat_distance, alpha=0.5):
+        """log of the initial match matrix: -beta (distance - alpha); alpha a float or [B]"""
+        if not isinstance(alpha, float):
+            alpha = alpha[:, None, None]
+        return -beta[:, None, None] * (feat_distance - alpha)
+
+    @staticmethod
+    def split_normals(data):
+        """[B,N,6] -> xyz, normals; [B,N,3] -> xyz and zero normals"""
+        if data.shape[2] == 6:
+            return data[:, :, :3], data[:, :, 3:6]
+        if data.shape[2] == 3:
+            return data, torch.zeros_like(data)
+        raise ValueError(f"RPMNet takes clouds [B,N,3] or [B,N,6], got {tuple(data.shape)}")
+
+    def spam(self, xyz_template, norm_template, xyz_source, norm_source):
+        """one round of the op sequence: parameters, features of both clouds, affinity, Sinkhorn -> weighted template [B,J,3]"""
+        self.beta, self.alpha = self.weights_net([xyz_source, xyz_template])
+        self.feat_source = self.feat_extractor(xyz_source, norm_source)
+        self.feat_template = self.feat_extractor(xyz_template, norm_template)
+        self.affinity = self.compute_affinity(self.beta, match_features(self.feat_source, self.feat_template), alpha=self.alpha)
+        self.perm_matrix = torch.exp(sinkhorn(self.affinity, n_iters=self.num_sk_iter, slack=self.add_slack))
+        return self.perm_matrix @ xyz_template / (torch.sum(self.perm_matrix, dim=2, keepdim=True) + _EPS)
+
+    def fusable(self, template, source):
+        """the fused route's gate: FUSED, the slack Sinkhorn, device fp32 clouds, nothing to differentiate in either network,
+        and a feature network whose own gate agrees"""
+        fx = self.feat_extractor
+        return (FUSED and self.add_slack and hasattr(fx, "fused_features") and _fused.fusable(self, template, source)
+                and fx.fusable(template, source))
+
+    def _result(self, source, transforms, gammas, perms, weighted, beta, alpha):
+        last = transforms[-1]
+        # [R t; 0 0 0 1] built on the tensor's own device: convert2transformation makes its bottom row on the host and copies it
+        # over, which a stream capture refuses
+        est_T = torch.zeros((last.shape[0], 4, 4), dtype=last.dtype, device=last.device)
+        est_T[:, :3, :] = last[:, :3, :]
+        est_T[:, 3, 3] = 1
+        moved = torch.bmm(est_T[:, :3, :3], source[:, :, :3].permute(0, 2, 1)).permute(0, 2, 1) + est_T[:, :3, 3].unsqueeze(1)
+        return {'est_R': est_T[:, :3, :3], 'est_t': est_T[:, :3, 3], 'est_T': est_T, 'transformed_source': moved,
+                'perm_matrices_init': gammas, 'perm_matrices': perms, 'weighted_template': weighted, 'beta': beta,
+                'alpha': alpha, 'transforms': transforms}
+
+    def _forward_fused(self, template, source, max_iterations):
+        """the fused route: the result dict with 'beta' and 'alpha' as device tensors [iterations,B]; nothing is read back"""
+        fx = self.feat_extractor
+        xyz_t, xyz_s = f32c(template[:, :, :3]), f32c(source[:, :, :3])
+        norm_t = f32c(template[:, :, 3:6]) if template.shape[2] == 6 else None
+        norm_s = f32c(source[:, :, 3:6]) if source.shape[2] == 6 else None
+        if template.shape[2] not in (3, 6) or source.shape[2] not in (3, 6):
+            raise ValueError(f"RPMNet takes clouds [B,N,3] or [B,N,6], got {tuple(template.shape)} and {tuple(source.shape)}")
+        self.feat_template = fx.fused_features(xyz_t, norm_t)                    # once: later iterations reuse it
+        cur, cur_n = xyz_s, norm_s
+        transforms, gammas, perms, weighted, betas, alphas = [], [], [], [], [], []
+        for _ in range(max_iterations):
+            self.beta, self.alpha = self.weights_net([cur, xyz_t])
+            self.feat_source = fx.fused_features(cur, cur_n)
+            dist = _device_square_distance(self.feat_source, self.feat_template)
+            self.affinity = self.compute_affinity(self.beta, dist, alpha=self.alpha)
+            _, self.perm_matrix, rowsum, wt = sinkhorn_slack(self.affinity, self.num_sk_iter, xyz_ref=xyz_t, want_log=False,
+                                                             want_perm=True)
+            T = rigid_transform_weighted(xyz_s, wt, rowsum)
+            if norm_s is None:
+                cur = se3_transform(T, xyz_s)
+            else:
+                cur, cur_n = se3_transform(T, xyz_s, norm_s)
+            transforms.append(T)
+            gammas.append(torch.exp(self.affinity))
+            perms.append(self.perm_matrix)
+            weighted.append(wt)
+            betas.append(self.beta)
+            alphas.append(self.alpha)
+        return self._result(source, transforms, gammas, perms, weighted, torch.stack(betas), torch.stack(alphas))
+
+    def forward(self, template, source, max_iterations: int = 1):
+        """template [B,K,3|6], source [B,J,3|6] (xyz, or xyz and normals) -> the reference's dict: est_R, est_t, est_T (source ->
+        template), transformed_source, and per iteration perm_matrices_init, perm_matrices, weighted_template, transforms, with
+        beta and alpha as numpy [iterations,B]"""
+        if self.fusable(template, source):
+            with on_device_of(template, source):
+                result = self._forward_fused(template, source, max_iterations)
+            result['beta'], result['alpha'] = to_numpy(result['beta']), to_numpy(result['alpha'])
+            return result
+
+        xyz_t, norm_t = self.split_normals(template)
+        xyz_s, norm_s = self.split_normals(source)
+        cur, cur_n = xyz_s, norm_s
+        transforms, gammas, perms, weighted, betas, alphas = [], [], [], [], [], []
+        for _ in range(max_iterations):
+            wt = self.spam(xyz_t, norm_t, cur, cur_n)
+            T = compute_rigid_transform(xyz_s, wt, weights=torch.sum(self.perm_matrix, dim=2))
+            cur, cur_n = se3_transform(T.detach(), xyz_s, norm_s)                # always the ORIGINAL source, moved
+            transforms.append(T)
+            gammas.append(torch.exp(self.affinity))
+            perms.append(self.perm_matrix)
+            weighted.append(wt)
+            betas.append(self.beta.detach())
+            alphas.append(self.alpha.detach())
+        return self._result(source, transforms, gammas, perms, weighted, to_numpy(torch.stack(betas)), to_numpy(torch.stack(alphas)))
