@@ -15,3 +15,4 @@ from .masknet2 import MaskNet2
 from .deepgmr import DeepGMR
 from .ppfnet import PPFNet
 from .rpmnet import RPMNet
+from .pointconv import create_pointconv
