@@ -16,3 +16,4 @@ from .deepgmr import DeepGMR
 from .ppfnet import PPFNet
 from .rpmnet import RPMNet
 from .pointconv import create_pointconv
+from .prnet import PRNet
