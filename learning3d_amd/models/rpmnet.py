@@ -24,6 +24,11 @@ Two routes:
     the parameter network in torch, PPFNet.fused_features of the moved source, the affinity from utils.square_distance,
     l3d_sinkhorn_slack (potentials only, the padded matrix is never written; it also gives the row sums and the weighted template
     points) and l3d_rigid_transform_weighted (3x3 SVD on the device).  No host read inside the loop.
+Training (a parameter requires a gradient, neither cloud does): the op-sequence loop, whose feature network then takes its
+differentiable HIP route (PPFNet.train_features); the template's features are computed once per forward and the tensor is reused
+by the later iterations, autograd adding the gradients of its uses.  Sinkhorn, the affinity, the weighted Kabsch step and
+ParameterPredictionNet stay torch autograd.  _fused.TRAIN_HIP = False, or a cloud that requires a gradient, gives the plain op
+sequence for both clouds.
 ParameterPredictionNet's [B,1024,J+K] stack stays in torch on both routes.
 _lib.LAUNCH_LOG shows the route: l3d_ppf_group and l3d_gn_conv appear on the fused one only (the public sinkhorn takes
 l3d_sinkhorn_slack on device fp32 tensors without autograd on either route, unless FUSED is off)."""
@@ -35,7 +40,7 @@ import torch.nn.functional as F
 from .. import _lib
 from .._lib import call, f32c, on_device_of
 from ..utils import angle_difference, square_distance as _device_square_distance
-from .ppfnet import PPFNet, _device_ops_take, _square_distance
+from .ppfnet import PPFNet, _device_ops_take, _square_distance, op_sequence_only
 from . import _fused
 
 _EPS = 1e-5  # To prevent division by zero
@@ -208,11 +213,12 @@ class RPMNet(nn.Module):
             return data, torch.zeros_like(data)
         raise ValueError(f"RPMNet takes clouds [B,N,3] or [B,N,6], got {tuple(data.shape)}")
 
-    def spam(self, xyz_template, norm_template, xyz_source, norm_source):
-        """one round of the op sequence: parameters, features of both clouds, affinity, Sinkhorn -> weighted template [B,J,3]"""
+    def spam(self, xyz_template, norm_template, xyz_source, norm_source, feat_template=None):
+        """one round of the op sequence: parameters, features of both clouds, affinity, Sinkhorn -> weighted template [B,J,3].
+        feat_template: the template's features from an earlier round, used instead of computing them again"""
         self.beta, self.alpha = self.weights_net([xyz_source, xyz_template])
         self.feat_source = self.feat_extractor(xyz_source, norm_source)
-        self.feat_template = self.feat_extractor(xyz_template, norm_template)
+        self.feat_template = self.feat_extractor(xyz_template, norm_template) if feat_template is None else feat_template
         self.affinity = self.compute_affinity(self.beta, match_features(self.feat_source, self.feat_template), alpha=self.alpha)
         self.perm_matrix = torch.exp(sinkhorn(self.affinity, n_iters=self.num_sk_iter, slack=self.add_slack))
         return self.perm_matrix @ xyz_template / (torch.sum(self.perm_matrix, dim=2, keepdim=True) + _EPS)
@@ -277,12 +283,23 @@ class RPMNet(nn.Module):
             result['beta'], result['alpha'] = to_numpy(result['beta']), to_numpy(result['alpha'])
             return result
 
+        # the feature network's differentiable HIP route (PPFNet.train_features) serves a pair only as a whole: with one cloud that
+        # requires a gradient both take the op sequence.  On that route the template's features are computed once and the tensor is
+        # reused by the later iterations (GroupNorm has no running state: the same values; autograd adds the gradients of its uses)
+        fx = self.feat_extractor
+        hip_train = hasattr(fx, "trains_on_hip") and fx.trains_on_hip(template, source)
+        if hip_train:
+            return self._forward_op_sequence(template, source, max_iterations, True)
+        with op_sequence_only():
+            return self._forward_op_sequence(template, source, max_iterations, False)
+
+    def _forward_op_sequence(self, template, source, max_iterations, reuse_template):
         xyz_t, norm_t = self.split_normals(template)
         xyz_s, norm_s = self.split_normals(source)
         cur, cur_n = xyz_s, norm_s
         transforms, gammas, perms, weighted, betas, alphas = [], [], [], [], [], []
-        for _ in range(max_iterations):
-            wt = self.spam(xyz_t, norm_t, cur, cur_n)
+        for it in range(max_iterations):
+            wt = self.spam(xyz_t, norm_t, cur, cur_n, feat_template=self.feat_template if reuse_template and it else None)
             T = compute_rigid_transform(xyz_s, wt, weights=torch.sum(self.perm_matrix, dim=2))
             cur, cur_n = se3_transform(T.detach(), xyz_s, norm_s)                # always the ORIGINAL source, moved
             transforms.append(T)

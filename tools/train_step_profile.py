@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Wall time vs GPU time of training steps on the HIP training path: DGCNN features + max-pool loss,
-PCN + Chamfer (examples/train_pcn.py:70-91).  Prints wall per step, the sum of kernel times per step and the top kernels."""
+PCN + Chamfer (examples/train_pcn.py:70-91); `--only flownet dcp rpmnet`: the named extra steps alone (RPMNet: 2 iterations on
+PPFNet's differentiable HIP route, RPMNET_B clouds).  Prints wall per step, the sum of kernel times per step and the top kernels."""
 import os
 import sys
 import time
@@ -109,6 +110,31 @@ def extra(which):
             loss.backward()
             opt.step()
         run(f"DCP-v2 train step (B {os.environ.get('DCP_B', '8')}, N 1024, emb 512; examples/train_dcp.py)", make, step, iters=3)
+    if "rpmnet" in which:
+        from learning3d_amd.losses import FrobeniusNormLoss
+        from learning3d_amd.models import RPMNet
+        B = int(os.environ.get("RPMNET_B", "8"))
+
+        def make():
+            net = RPMNet().cuda().train()
+            g = torch.Generator().manual_seed(0)
+            xyz = torch.rand(B, 1024, 3, generator=g) * 2 - 1
+            nrm = torch.nn.functional.normalize(torch.randn(B, 1024, 3, generator=g), dim=-1)
+            t = torch.cat([xyz, nrm], -1).cuda()
+            s_ = torch.cat([xyz + 0.05, nrm], -1).cuda()
+            return net, torch.optim.Adam(net.parameters(), lr=1e-4), (t, s_, torch.eye(4, device="cuda").repeat(B, 1, 1))
+
+        loss_fn = FrobeniusNormLoss()
+
+        def step(net, opt, data):
+            t, s_, igt = data
+            opt.zero_grad(set_to_none=True)
+            out = net(t, s_, 2)
+            loss = loss_fn(out["est_T"], igt) + torch.stack([pm.sum(2).mean() for pm in out["perm_matrices"]]).mean()
+            loss.backward()
+            opt.step()
+        run(f"RPMNet train step (B {B}, 1024 points with normals, 64 neighbours, 2 iterations; the loss of tools/rpmnet_train_bench.py)",
+            make, step, iters=3)
 
 
 if __name__ == "__main__":
