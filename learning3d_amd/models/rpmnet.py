@@ -26,9 +26,12 @@ Two routes:
     points) and l3d_rigid_transform_weighted (3x3 SVD on the device).  No host read inside the loop.
 Training (a parameter requires a gradient, neither cloud does): the op-sequence loop, whose feature network then takes its
 differentiable HIP route (PPFNet.train_features); the template's features are computed once per forward and the tensor is reused
-by the later iterations, autograd adding the gradients of its uses.  Sinkhorn, the affinity, the weighted Kabsch step and
-ParameterPredictionNet stay torch autograd.  _fused.TRAIN_HIP = False, or a cloud that requires a gradient, gives the plain op
-sequence for both clouds.
+by the later iterations, autograd adding the gradients of its uses.  The matching stage -- affinity, Sinkhorn, exp, row sums and
+weighted template -- is one differentiable unit on HIP (RPMNet._Match, gate RPMNet.matches_on_hip, A/B switch MATCH_HIP):
+l3d_sinkhorn_slack_keep keeps the fp64 potentials of every iteration and l3d_sinkhorn_slack_backward runs the reverse sweep from
+them, so no padded [B,J+1,K+1] tensor exists and the Kabsch weights are the unit's own row sums.  The feature distance, the
+weighted Kabsch step (torch.svd) and ParameterPredictionNet stay torch autograd.  _fused.TRAIN_HIP = False, or a cloud that
+requires a gradient, gives the plain op sequence for both clouds and for the matching.
 ParameterPredictionNet's [B,1024,J+K] stack stays in torch on both routes.
 _lib.LAUNCH_LOG shows the route: l3d_ppf_group and l3d_gn_conv appear on the fused one only (the public sinkhorn takes
 l3d_sinkhorn_slack on device fp32 tensors without autograd on either route, unless FUSED is off)."""
@@ -41,10 +44,12 @@ from .. import _lib
 from .._lib import call, f32c, on_device_of
 from ..utils import angle_difference, square_distance as _device_square_distance
 from .ppfnet import PPFNet, _device_ops_take, _square_distance, op_sequence_only
+from .ppfnet import _TLS as _ppfnet_tls
 from . import _fused
 
 _EPS = 1e-5  # To prevent division by zero
 FUSED = True                 # False: the op sequence for every input (A/B: tools/rpmnet_bench.py)
+MATCH_HIP = True             # False: the matching stage of a training step on torch autograd (A/B: tools/rpmnet_train_bench.py)
 
 
 def _block(layer, groups, width):
@@ -129,6 +134,37 @@ def sinkhorn_slack(log_alpha, n_iters, xyz_ref=None, eps=_EPS, want_log=True, wa
     ws = torch.empty(_lib.lib().l3d_sinkhorn_workspace_bytes(B, J, K) // 8, dtype=torch.float64, device=dev)
     call("l3d_sinkhorn_slack", A, B, J, K, int(n_iters), xyz_ref, float(eps), log_perm, perm, rowsum, weighted, ws)
     return log_perm, perm, rowsum, weighted
+
+
+def sinkhorn_slack_keep(log_alpha, n_iters, xyz_ref, eps=_EPS):
+    """l3d_sinkhorn_slack_keep on contiguous device fp32 log_alpha [B,J,K], xyz_ref [B,K,3] -> (perm, rowsum [B,J], weighted [B,J,3],
+    potentials fp64 [n_iters,B,J+K]); the first three are l3d_sinkhorn_slack's bits"""
+    B, J, K = log_alpha.shape
+    dev = log_alpha.device
+    perm = torch.empty_like(log_alpha)
+    rowsum = torch.empty((B, J), dtype=torch.float32, device=dev)
+    weighted = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
+    potentials = torch.empty((int(n_iters), B, J + K), dtype=torch.float64, device=dev)
+    call("l3d_sinkhorn_slack_keep", log_alpha, B, J, K, int(n_iters), xyz_ref, float(eps), None, perm, rowsum, weighted,
+         potentials if n_iters else None)
+    return perm, rowsum, weighted, potentials
+
+
+def sinkhorn_slack_backward(log_alpha, potentials, xyz_ref=None, eps=_EPS, d_perm=None, d_rowsum=None, d_weighted=None, d_affinity=None,
+                            dist=None, beta=None, alpha=None, want_beta=False, want_alpha=False):
+    """l3d_sinkhorn_slack_backward: contiguous device fp32 tensors, potentials from sinkhorn_slack_keep, whichever cotangents arrived
+    -> (d_out [B,J,K], d_beta [B] or None, d_alpha [B] or None).  With dist, beta, alpha d_out is the gradient at dist, else at
+    log_alpha"""
+    B, J, K = log_alpha.shape
+    n = potentials.shape[0]
+    dev = log_alpha.device
+    d_out = torch.empty_like(log_alpha)
+    d_beta = torch.empty(B, dtype=torch.float32, device=dev) if want_beta else None
+    d_alpha = torch.empty(B, dtype=torch.float32, device=dev) if want_alpha else None
+    ws = torch.empty(_lib.lib().l3d_sinkhorn_backward_workspace_bytes(B, J, K, n) // 8, dtype=torch.float64, device=dev)
+    call("l3d_sinkhorn_slack_backward", log_alpha, potentials if n else None, B, J, K, n, xyz_ref, float(eps), d_perm, d_rowsum,
+         d_weighted, d_affinity, dist, beta, alpha, d_out, d_beta, d_alpha, ws)
+    return d_out, d_beta, d_alpha
 
 
 def sinkhorn(log_alpha, n_iters: int = 5, slack: bool = True, eps: float = -1) -> torch.Tensor:
@@ -219,9 +255,59 @@ class RPMNet(nn.Module):
         self.beta, self.alpha = self.weights_net([xyz_source, xyz_template])
         self.feat_source = self.feat_extractor(xyz_source, norm_source)
         self.feat_template = self.feat_extractor(xyz_template, norm_template) if feat_template is None else feat_template
-        self.affinity = self.compute_affinity(self.beta, match_features(self.feat_source, self.feat_template), alpha=self.alpha)
-        self.perm_matrix = torch.exp(sinkhorn(self.affinity, n_iters=self.num_sk_iter, slack=self.add_slack))
-        return self.perm_matrix @ xyz_template / (torch.sum(self.perm_matrix, dim=2, keepdim=True) + _EPS)
+        dist = match_features(self.feat_source, self.feat_template)
+        self.affinity, self.perm_matrix, self._match_rowsum, weighted = self.match_stage(dist, self.beta, self.alpha, xyz_template)
+        return weighted
+
+    def match_stage(self, dist, beta, alpha, xyz_ref):
+        """feature distances [B,J,K], beta, alpha, xyz_ref [B,K,3] -> (affinity, perm, rowsum, weighted [B,J,3]): RPMNet._Match where
+        matches_on_hip holds (rowsum [B,J] is then the unit's own output), else the op sequence (rowsum None: the caller sums perm)"""
+        if self.matches_on_hip(dist, beta, alpha, xyz_ref):
+            with on_device_of(dist):
+                return self._Match.apply(dist, beta, alpha, xyz_ref, self.num_sk_iter)
+        affinity = self.compute_affinity(beta, dist, alpha=alpha)
+        perm = torch.exp(sinkhorn(affinity, n_iters=self.num_sk_iter, slack=self.add_slack))
+        return affinity, perm, None, perm @ xyz_ref / (torch.sum(perm, dim=2, keepdim=True) + _EPS)
+
+    def matches_on_hip(self, dist, beta, alpha, xyz_ref):
+        """the gate of the matching stage's differentiable HIP route: MATCH_HIP and _fused.TRAIN_HIP, grad mode on and not inside
+        op_sequence_only, the slack Sinkhorn, device fp32 tensors with beta and alpha [B], a template that requires no gradient and
+        at least one of dist, beta, alpha that does"""
+        tensors = (dist, beta, alpha, xyz_ref)
+        return (MATCH_HIP and _fused.TRAIN_HIP and torch.is_grad_enabled() and not getattr(_ppfnet_tls, "op_sequence", False)
+                and self.add_slack and all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in tensors)
+                and dist.dim() == 3 and beta.shape == alpha.shape == dist.shape[:1] and not xyz_ref.requires_grad
+                and (dist.requires_grad or beta.requires_grad or alpha.requires_grad))
+
+    # A class of the model, as PPFNet._Train is: tests/test_gpu_views_backward.py pins the set of module-level autograd.Functions.
+    class _Match(torch.autograd.Function):
+        """dist [B,J,K], beta [B], alpha [B], xyz_ref [B,K,3], n_iters -> affinity, perm, rowsum [B,J], weighted [B,J,3]: the chain
+        compute_affinity -> sinkhorn -> exp -> row sums -> weighted template as one unit, differentiable with respect to dist, beta
+        and alpha.  forward: the affinity by compute_affinity's own torch expression (the op sequence's bits), then
+        l3d_sinkhorn_slack_keep.  Kept for the backward: the inputs, the affinity and the fp64 potentials [n,B,J+K]; perm is not,
+        the backward forms P again in fp64.  backward: one l3d_sinkhorn_slack_backward call on whichever cotangents arrived, with
+        the fold's d_beta / d_alpha only where beta / alpha needs a gradient; None for xyz_ref."""
+
+        @staticmethod
+        def forward(ctx, dist, beta, alpha, xyz_ref, n_iters):
+            dist, beta, alpha, xyz_ref = f32c(dist.detach()), f32c(beta.detach()), f32c(alpha.detach()), f32c(xyz_ref.detach())
+            affinity = -beta[:, None, None] * (dist - alpha[:, None, None])      # compute_affinity's expression
+            perm, rowsum, weighted, potentials = sinkhorn_slack_keep(affinity, n_iters, xyz_ref)
+            ctx.save_for_backward(dist, beta, alpha, xyz_ref, affinity, potentials)
+            ctx.set_materialize_grads(False)
+            return affinity, perm, rowsum, weighted
+
+        @staticmethod
+        def backward(ctx, d_affinity, d_perm, d_rowsum, d_weighted):
+            dist, beta, alpha, xyz_ref, affinity, potentials = ctx.saved_tensors
+            given = [None if g is None else f32c(g) for g in (d_perm, d_rowsum, d_weighted, d_affinity)]
+            need_dist, need_beta, need_alpha = ctx.needs_input_grad[:3]
+            if all(g is None for g in given) or not (need_dist or need_beta or need_alpha):
+                return None, None, None, None, None
+            with on_device_of(affinity):
+                d_dist, d_beta, d_alpha = sinkhorn_slack_backward(affinity, potentials, xyz_ref, _EPS, *given, dist=dist, beta=beta,
+                                                                  alpha=alpha, want_beta=need_beta, want_alpha=need_alpha)
+            return d_dist if need_dist else None, d_beta, d_alpha, None, None
 
     def fusable(self, template, source):
         """the fused route's gate: FUSED, the slack Sinkhorn, device fp32 clouds, nothing to differentiate in either network,
@@ -300,7 +386,9 @@ class RPMNet(nn.Module):
         transforms, gammas, perms, weighted, betas, alphas = [], [], [], [], [], []
         for it in range(max_iterations):
             wt = self.spam(xyz_t, norm_t, cur, cur_n, feat_template=self.feat_template if reuse_template and it else None)
-            T = compute_rigid_transform(xyz_s, wt, weights=torch.sum(self.perm_matrix, dim=2))
+            # the matching unit's own row sums where it ran: a torch.sum of its perm would send a dense d_perm back to it
+            rowsum = getattr(self, "_match_rowsum", None)
+            T = compute_rigid_transform(xyz_s, wt, weights=torch.sum(self.perm_matrix, dim=2) if rowsum is None else rowsum)
             cur, cur_n = se3_transform(T.detach(), xyz_s, norm_s)                # always the ORIGINAL source, moved
             transforms.append(T)
             gammas.append(torch.exp(self.affinity))
@@ -308,4 +396,5 @@ class RPMNet(nn.Module):
             weighted.append(wt)
             betas.append(self.beta.detach())
             alphas.append(self.alpha.detach())
+        self._match_rowsum = None
         return self._result(source, transforms, gammas, perms, weighted, to_numpy(torch.stack(betas)), to_numpy(torch.stack(alphas)))

@@ -7,6 +7,16 @@ autograd -- what every build before this route ran):
              a stand-in for an inlier term, backward, Adam
   kernels    each streaming kernel of rpmnet_train.hip alone at the pre-pool shape [B,96 or 192,64 * points], with the bytes it has to
              move (from the shapes) over its time
+  matching   the matching stage (affinity, Sinkhorn, exp, row sums, weighted template) on RPMNet._Match against torch autograd of the
+             same build (rpmnet.MATCH_HIP = False, PPFNet's HIP route on on both sides):
+               matching_*        forward + backward of the stage alone at [B,points,points], the step's cotangents
+               step_match_*      the whole step with MATCH_HIP on and off
+               matching_kernels  l3d_sinkhorn_slack_keep and l3d_sinkhorn_slack_backward alone.  The backward is one entry point;
+                                 its passes are told apart by n_iters: 0 is the first row pass and the output pass, and a further
+                                 iteration adds one row and one column reduction and two exponentials per element of the output
+                                 pass.  Bytes: log_alpha once per pass, the dense cotangent and dist where a pass reads them, d_out
+               split             forward + backward of each other part of an iteration alone at the step's shapes:
+                                 ParameterPredictionNet, the feature distance, the weighted Kabsch step
 
 The two sides of each pair run interleaved, round by round, so that clock and thermal drift hits both alike; medians over the
 rounds.  Peak memory is torch.cuda.max_memory_allocated over one warm round of each side, above what was allocated before it.
@@ -23,7 +33,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from learning3d_amd.losses import FrobeniusNormLoss                   # noqa: E402
-from learning3d_amd.models import RPMNet, _fused, ppfnet               # noqa: E402
+from learning3d_amd.models import RPMNet, _fused, ppfnet, rpmnet       # noqa: E402
 
 
 def timed(fn, hip, reps=1):
@@ -47,6 +57,61 @@ def peak(fn, hip):
     base = torch.cuda.memory_allocated()
     timed(fn, hip)
     return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+
+
+def with_match(fn, on):
+    """fn with rpmnet.MATCH_HIP = on"""
+    def run():
+        prev, rpmnet.MATCH_HIP = rpmnet.MATCH_HIP, on
+        try:
+            fn()
+        finally:
+            rpmnet.MATCH_HIP = prev
+    return run
+
+
+def pair(line, name, fn, rounds):
+    """ms (median, min, max) and peak of fn with MATCH_HIP on and off, interleaved round by round"""
+    sides = {"hip": with_match(fn, True), "torch": with_match(fn, False)}
+    ms = {k: [] for k in sides}
+    for f in sides.values():
+        timed(f, True)
+    for _ in range(rounds):
+        for k, f in sides.items():
+            ms[k].append(timed(f, True))
+    for k, f in sides.items():
+        line[f"{name}_ms_{k}"] = [round(statistics.median(ms[k]), 3), round(min(ms[k]), 3), round(max(ms[k]), 3)]
+        line[f"{name}_peak_mib_{k}"] = round(peak(f, True), 1)
+
+
+def matching_kernels(B, N, dev, rounds, n_iters=5):
+    """-> {case: (ms, GB/s)} of the two entry points alone at [B,N,N]"""
+    g = torch.Generator(device=dev).manual_seed(2)
+    dist = torch.rand((B, N, N), device=dev, generator=g) * 2
+    beta, alpha = torch.rand(B, device=dev, generator=g) + 1, torch.rand(B, device=dev, generator=g) * 0.5 + 0.5
+    x = torch.rand((B, N, 3), device=dev, generator=g)
+    A = (-beta[:, None, None] * (dist - alpha[:, None, None])).contiguous()
+    dp, dr, dw = torch.randn((B, N, N), device=dev, generator=g), torch.randn((B, N), device=dev, generator=g), torch.randn((B, N, 3), device=dev, generator=g)
+    tensor = B * N * N * 4
+    pots = {n: rpmnet.sinkhorn_slack_keep(A, n, x)[3] for n in (0, 1, n_iters)}
+
+    def back(n):
+        return lambda: rpmnet.sinkhorn_slack_backward(A, pots[n], x, 1e-5, d_perm=dp, d_rowsum=dr, d_weighted=dw, dist=dist, beta=beta,
+                                                      alpha=alpha, want_beta=True, want_alpha=True)
+    # passes over log_alpha: keep 2 n + 1 (+ perm written); backward 3 + 2 n - 1 for n >= 1, 2 for n = 0; d_perm in the row, column and
+    # output pass, dist and d_out in the output pass
+    cases = {"sinkhorn_slack_keep": ((2 * n_iters + 2) * tensor, lambda: rpmnet.sinkhorn_slack_keep(A, n_iters, x)),
+             "sinkhorn_slack_backward_n0": ((2 + 2 + 2) * tensor, back(0)),
+             "sinkhorn_slack_backward_n1": ((4 + 3 + 2) * tensor, back(1)),
+             f"sinkhorn_slack_backward_n{n_iters}": ((2 * n_iters + 2 + 3 + 2) * tensor, back(n_iters))}
+    res = {}
+    for name, (nbytes, fn) in cases.items():
+        timed(fn, True)
+        ms = statistics.median(timed(fn, True, 5) for _ in range(rounds))
+        res[name] = {"ms": round(ms, 4), "GB_per_s": round(nbytes / ms / 1e6, 1)}
+    per_iter = (res[f"sinkhorn_slack_backward_n{n_iters}"]["ms"] - res["sinkhorn_slack_backward_n1"]["ms"]) / (n_iters - 1)
+    res["backward_ms_per_further_iteration"] = round(per_iter, 4)
+    return res
 
 
 def kernel_rates(B, C, K, N, dev, rounds):
@@ -95,6 +160,7 @@ def main():
     ap.add_argument("--points", type=int, default=1024)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--no-matching", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     N = a.points
@@ -137,6 +203,42 @@ def main():
             line[name + "_ms_op_sequence"] = round(statistics.median(ms[False]), 3)
             line[name + "_peak_mib_hip"] = round(peak(fn, True), 1)
             line[name + "_peak_mib_op_sequence"] = round(peak(fn, False), 1)
+        if not a.no_matching:
+            dist0 = torch.rand(B, N, N, device=dev) * 2
+            feat_s = torch.nn.functional.normalize(torch.randn(B, N, fx.postpool[6].out_channels, device=dev), dim=-1)
+            feat_t = torch.nn.functional.normalize(torch.randn(B, N, fx.postpool[6].out_channels, device=dev), dim=-1)
+            wts = torch.rand(B, N, device=dev)
+            moved = xyz @ R.t() + 0.1
+
+            def matching():
+                d = dist0.clone().requires_grad_()
+                beta = torch.full((B,), 1.5, device=dev, requires_grad=True)
+                alpha = torch.full((B,), 0.6, device=dev, requires_grad=True)
+                _, perm, rowsum, wt = net.match_stage(d, beta, alpha, xyz)
+                rows = rowsum if rowsum is not None else torch.sum(perm, dim=2)
+                (perm.sum(2).mean() + (wt * wt).sum() + (rows * wts).sum()).backward()
+
+            def parameter_net():
+                net.zero_grad(set_to_none=True)
+                beta, alpha = net.weights_net([moved, xyz])
+                (beta.sum() + alpha.sum()).backward()
+
+            def feature_distance():
+                fs, ft = feat_s.clone().requires_grad_(), feat_t.clone().requires_grad_()
+                (rpmnet.match_features(fs, ft) * dist0).sum().backward()
+
+            def kabsch():
+                w, b = wts.clone().requires_grad_(), xyz.clone().requires_grad_()
+                rpmnet.compute_rigid_transform(moved, b, w).sum().backward()
+
+            pair(line, "matching", matching, a.rounds)
+            pair(line, "step_match", step, a.rounds)
+            split = {}
+            for name, fn in (("parameter_net", parameter_net), ("feature_distance", feature_distance), ("kabsch", kabsch)):
+                timed(fn, True)
+                split[name + "_ms"] = round(statistics.median(timed(fn, True) for _ in range(a.rounds)), 3)
+            line["split"] = split
+            line["matching_kernels"] = matching_kernels(B, N, dev, a.rounds, net.num_sk_iter)
         if not a.no_kernels:
             del net, opt
             torch.cuda.empty_cache()
