@@ -21,7 +21,8 @@ Two routes:
     add_slack=False, a Sinkhorn eps > 0, metric='angle', and any feature network without a `fused_features` the kernels take.
   * fused (FUSED, device fp32, nothing to differentiate, add_slack, a fusable PPFNet): RPMNet._forward_fused.  The template's
     features are computed once and reused by the later iterations (GroupNorm has no running state: the same bits); per iteration
-    the parameter network in torch, PPFNet.fused_features of the moved source, the affinity from utils.square_distance,
+    the parameter network (ParameterPredictionNet.fused_forward where its gate holds: the pre-pool stack on l3d_gn_conv and
+    l3d_gn_conv_gpool, the head in torch; switch PARAM_HIP), PPFNet.fused_features of the moved source, the affinity from utils.square_distance,
     l3d_sinkhorn_slack (potentials only, the padded matrix is never written; it also gives the row sums and the weighted template
     points) and l3d_rigid_transform_weighted (3x3 SVD on the device).  No host read inside the loop.
 Training (a parameter requires a gradient, neither cloud does): the op-sequence loop, whose feature network then takes its
@@ -30,11 +31,13 @@ by the later iterations, autograd adding the gradients of its uses.  The matchin
 weighted template -- is one differentiable unit on HIP (RPMNet._Match, gate RPMNet.matches_on_hip, A/B switch MATCH_HIP):
 l3d_sinkhorn_slack_keep keeps the fp64 potentials of every iteration and l3d_sinkhorn_slack_backward runs the reverse sweep from
 them, so no padded [B,J+1,K+1] tensor exists and the Kabsch weights are the unit's own row sums.  The feature distance, the
-weighted Kabsch step (torch.svd) and ParameterPredictionNet stay torch autograd.  _fused.TRAIN_HIP = False, or a cloud that
-requires a gradient, gives the plain op sequence for both clouds and for the matching.
-ParameterPredictionNet's [B,1024,J+K] stack stays in torch on both routes.
-_lib.LAUNCH_LOG shows the route: l3d_ppf_group and l3d_gn_conv appear on the fused one only (the public sinkhorn takes
-l3d_sinkhorn_slack on device fp32 tensors without autograd on either route, unless FUSED is off)."""
+weighted Kabsch step (torch.svd) and the parameter network's post-pool head stay torch autograd.  ParameterPredictionNet's
+pre-pool stack is differentiable on HIP too (ParameterPredictionNet._Train, gate trains_on_hip, A/B switch PARAM_HIP): its last
+layer, 128 -> 1024 channels over all J + K positions into a maximum, never writes its [B,1024,J+K] output, forward
+(l3d_gn_conv_gpool) or backward (l3d_gn_gpool_backward forms it again).  _fused.TRAIN_HIP = False, or a cloud that requires a
+gradient, gives the plain op sequence for both clouds, for the matching and for the parameter network.
+_lib.LAUNCH_LOG shows the route: l3d_ppf_group and l3d_gn_conv appear on the fused and the training route only (the public
+sinkhorn takes l3d_sinkhorn_slack on device fp32 tensors without autograd on either route, unless FUSED is off)."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -43,21 +46,75 @@ import torch.nn.functional as F
 from .. import _lib
 from .._lib import call, f32c, on_device_of
 from ..utils import angle_difference, square_distance as _device_square_distance
-from .ppfnet import PPFNet, _device_ops_take, _square_distance, op_sequence_only
+from .ppfnet import PPFNet, _device_ops_take, _kernel_takes, _square_distance, gn_affine, gn_backward, gn_conv, gn_mean_rstd, gn_relu
+from .ppfnet import op_sequence_only
 from .ppfnet import _TLS as _ppfnet_tls
 from . import _fused
 
 _EPS = 1e-5  # To prevent division by zero
 FUSED = True                 # False: the op sequence for every input (A/B: tools/rpmnet_bench.py)
 MATCH_HIP = True             # False: the matching stage of a training step on torch autograd (A/B: tools/rpmnet_train_bench.py)
+PARAM_HIP = True             # False: ParameterPredictionNet's pre-pool stack in torch on every route (A/B: both tools above)
 
 
 def _block(layer, groups, width):
     return [layer, nn.GroupNorm(groups, width), nn.ReLU()]
 
 
+def gn_conv_gpool(x, in_a, in_s, weight, bias):
+    """l3d_gn_conv_gpool: x [B,Cin,P], in_a / in_s [B,Cin] or None, weight [Cout,Cin(,1)], bias [Cout] or None -> (ymax, ymin [B,Cout],
+    pmax, pmin int32 [B,Cout], moments fp64 [B,Cout,2]) of the convolution output over all P positions; the output is never stored"""
+    x = f32c(x)
+    B, Cin, P = x.shape
+    Cout = weight.shape[0]
+    w = f32c(weight.detach()).view(Cout, Cin)
+    dev = x.device
+    ymax = torch.empty((B, Cout), dtype=torch.float32, device=dev)
+    ymin = torch.empty_like(ymax)
+    pmax = torch.empty((B, Cout), dtype=torch.int32, device=dev)
+    pmin = torch.empty_like(pmax)
+    moments = torch.empty((B, Cout, 2), dtype=torch.float64, device=dev)
+    ws = torch.empty(_lib.lib().l3d_gn_conv_gpool_workspace_bytes(B, Cout, P) // 8, dtype=torch.float64, device=dev)
+    call("l3d_gn_conv_gpool", x, in_a, in_s, w, None if bias is None else f32c(bias.detach()), B, Cin, Cout, P, ymax, ymin, pmax, pmin,
+         moments, ws)
+    return ymax, ymin, pmax, pmin, moments
+
+
+def gn_gpool_backward(x, in_a, in_s, weight, bias, g, ext, pw, stat, gamma, groups, want_dz=True, want_gamma=True, want_beta=True):
+    """The backward of a conv -> GroupNorm -> ReLU -> maximum over all positions layer at the convolution output, which is formed
+    again from the forward's operands (x, in_a, in_s, weight, bias as gn_conv_gpool took them).  g [B,C] the gradient at the pooled
+    value times [pooled > 0]; ext, pw [B,C] the winning extreme and its position; stat from gn_mean_rstd; gamma [C].  The channel sums
+    S1 = g, S2 = g zhat(ext) in torch (fp64, [B,C]), l3d_gn_backward_reduce with count = P, l3d_gn_gpool_backward
+    -> (dz [B,C,P] or None, dgamma [C] or None, dbeta [C] or None)"""
+    x = f32c(x)
+    B, Cin, P = x.shape
+    Cc = weight.shape[0]
+    dev = x.device
+    gamma, g = f32c(gamma.detach()), f32c(g)
+    cpg = Cc // groups
+    s1 = g.double()
+    zhat = (ext.double() - stat[:, :, 0].repeat_interleave(cpg, 1)) * stat[:, :, 1].repeat_interleave(cpg, 1)
+    part = torch.stack([s1, s1 * zhat], -1).contiguous()
+    m = torch.empty((B, groups, 2), dtype=torch.float64, device=dev)
+    dgamma = torch.empty(Cc, dtype=torch.float32, device=dev) if want_gamma else None
+    dbeta = torch.empty(Cc, dtype=torch.float32, device=dev) if want_beta else None
+    call("l3d_gn_backward_reduce", part, gamma, B, Cc, int(groups), P, m, dgamma, dbeta)
+    dz = None
+    if want_dz:
+        dz = torch.empty((B, Cc, P), dtype=torch.float32, device=dev)
+        call("l3d_gn_gpool_backward", x, in_a, in_s, f32c(weight.detach()).view(Cc, Cin), None if bias is None else f32c(bias.detach()),
+             g, pw, stat, gamma, m, B, Cin, Cc, int(groups), P, dz)
+    return dz, dgamma, dbeta
+
+
 class ParameterPredictionNet(nn.Module):
-    """PointNet over both clouds (a fourth coordinate tells them apart) -> beta, alpha > 0 per pair"""
+    """PointNet over both clouds (a fourth coordinate tells them apart) -> beta, alpha > 0 per pair.
+    The pre-pool stack (five conv -> GroupNorm -> ReLU layers and the maximum over all J + K positions) has two HIP routes beside
+    the op sequence, both behind PARAM_HIP; the post-pool head (three Linear layers over B rows) is torch on every route.
+      * `fused_forward` (gate `fused_takes`; RPMNet._forward_fused calls it, `forward` never takes it on its own): layers 1-4 by
+        l3d_gn_conv + l3d_gn_affine, layer 5 by l3d_gn_conv_gpool, whose [B,1024,J+K] output is never written.
+      * `_Train` (gate `trains_on_hip`; `forward` dispatches to it): the same launch list under autograd, differentiable with respect
+        to the 20 pre-pool parameter tensors; the backward forms layer 5's output again (l3d_gn_gpool_backward)."""
 
     def __init__(self, weights_dim):
         super().__init__()
@@ -71,8 +128,170 @@ class ParameterPredictionNet(nn.Module):
         self.postpool = nn.Sequential(*_block(nn.Linear(1024, 512), 16, 512), *_block(nn.Linear(512, 256), 16, 256),
                                       nn.Linear(256, 2 + int(np.prod(weights_dim))))
 
+    def _layers(self):
+        """the five pre-pool convolutions in order, each with the GroupNorm behind it"""
+        pre = self.prepool
+        return [(pre[i], pre[i + 1]) for i in range(0, len(pre), 3)]
+
+    def _parameters_in_order(self):
+        """the pre-pool parameter tensors layer by layer: weight, bias of the convolution, weight, bias of the GroupNorm"""
+        return [p for pair in self._layers() for m in pair for p in (m.weight, m.bias) if p is not None]
+
+    def _kernels_take(self):
+        """layers of Conv1d(k = 1) -> affine GroupNorm -> ReLU with widths the kernels take, forward and as dgrad"""
+        layers = self._layers()
+        if not all(isinstance(c, nn.Conv1d) and c.kernel_size == (1,) and c.bias is not None and isinstance(n, nn.GroupNorm)
+                   and n.affine for c, n in layers):
+            return False
+        last = layers[-1][0]
+        # forward: l3d_gn_conv, the last layer l3d_gn_conv_gpool; dgrad of every layer but the first: l3d_gn_conv on the transpose
+        return (all(_kernel_takes(c.in_channels, c.out_channels) for c, _ in layers[:-1])
+                and all(_kernel_takes(c.out_channels, c.in_channels) for c, _ in layers[1:])
+                and last.out_channels % 16 == 0 and 16 <= last.out_channels <= _lib.L3D_GN_GPOOL_MAX_COUT
+                and 1 <= last.in_channels <= _lib.L3D_GN_CONV_MAX_CIN)
+
+    @staticmethod
+    def _clouds_fit(src, ref):
+        return (all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.shape[2] == 3
+                    for t in (src, ref)) and src.shape[0] == ref.shape[0] <= 65535)
+
+    def fused_takes(self, src, ref):
+        """the eval route's gate: PARAM_HIP, device fp32 clouds [B,J,3], [B,K,3], nothing to differentiate, widths the kernels take"""
+        return PARAM_HIP and self._clouds_fit(src, ref) and self._kernels_take() and _fused.fusable(self, src, ref)
+
+    def trains_on_hip(self, src, ref):
+        """the differentiable HIP route's gate: PARAM_HIP and _fused.TRAIN_HIP, grad mode on and not inside op_sequence_only, device
+        fp32 clouds that require no gradient themselves, affine GroupNorms and widths the kernels take, and a pre-pool parameter that
+        requires a gradient"""
+        return (PARAM_HIP and _fused.TRAIN_HIP and torch.is_grad_enabled() and not getattr(_ppfnet_tls, "op_sequence", False)
+                and self._clouds_fit(src, ref) and not src.requires_grad and not ref.requires_grad and self._kernels_take()
+                and any(p.requires_grad for p in self._parameters_in_order()))
+
+    @staticmethod
+    def _input(src, ref):
+        """[B,J,3], [B,K,3] -> [B,4,J+K] contiguous, the fourth channel 0 on the source and 1 on the reference"""
+        src = F.pad(src, (0, 1), mode='constant', value=0)
+        ref = F.pad(ref, (0, 1), mode='constant', value=1)
+        return torch.cat([src, ref], dim=1).permute(0, 2, 1).contiguous()
+
+    def _prepool_hip(self, x, keep=False):
+        """x [B,4,P] -> the pooled activation [B,C]; keep: also (ys, affs, stats, ext, pw) for the backward: the convolution outputs of
+        layers 1-4, every layer's a, s [B,C] and (mean, rstd), the winning extreme of layer 5 and its position [B,C]"""
+        P = x.shape[2]
+        layers = self._layers()
+        a = s = None
+        ys, affs, stats = [], [], []
+        for i, (conv, norm) in enumerate(layers):
+            if i < len(layers) - 1:
+                y, _, _, mom = gn_conv(x, a, s, conv.weight, conv.bias)
+            else:
+                ymax, ymin, pmax, pmin, mom = gn_conv_gpool(x, a, s, conv.weight, conv.bias)
+            if keep:
+                stats.append(gn_mean_rstd(mom, norm.num_groups, P, norm.eps))
+            a, s = gn_affine(mom, norm, P)
+            affs += [a, s]
+            if i < len(layers) - 1:
+                ys.append(y)
+                x = y
+        up = a >= 0
+        ext = torch.where(up, ymax, ymin)                  # the extreme the GroupNorm's sign turns into the maximum
+        pooled = self._pooled(a, s, ext)
+        return (pooled, (ys, affs, stats, ext, torch.where(up, pmax, pmin))) if keep else pooled
+
+    @staticmethod
+    def _pooled(a, s, ext):
+        return torch.relu(a * ext + s)
+
+    def _head(self, pooled):
+        raw = self.postpool(pooled)
+        return F.softplus(raw[:, 0]), F.softplus(raw[:, 1])
+
+    def fused_prepool(self, x):
+        """x = [src [B,J,3], ref [B,K,3]] -> the pooled pre-pool activation [B,1024]; device fp32, no autograd, no host read"""
+        with on_device_of(x[0]):
+            return self._prepool_hip(self._input(f32c(x[0]), f32c(x[1])))
+
+    def fused_forward(self, x):
+        """forward on the eval HIP route (the caller has asked fused_takes)"""
+        return self._head(self.fused_prepool(x))
+
+    # A class of the model, as PPFNet._Train and RPMNet._Match are: tests/test_gpu_views_backward.py pins the set of module-level
+    # autograd.Functions.  Its checks (view inputs, gradients that arrive as views) are held by tests/test_gpu_rpmnet_param.py.
+    class _Train(torch.autograd.Function):
+        """src [B,J,3], ref [B,K,3] -> the pooled activation [B,1024], differentiable with respect to the 20 pre-pool parameter
+        tensors.  forward: fused_prepool's launch list plus an l3d_gn_mean_rstd per layer.  Kept for the backward: the input [B,4,P],
+        the convolution outputs y1..y4, per layer a, s [B,C] and (mean, rstd), layer 5's winning extreme and its position [B,1024],
+        the parameters -- no [B,1024,P] tensor.  backward: layer 5 by gn_gpool_backward (its output formed again), then, last layer to
+        first as PPFNet._Train does, dW by l3d_wgrad on the operand l3d_gn_relu writes (released behind the wgrad), db from
+        l3d_channel_stats, du = W^T dz by l3d_gn_conv on the transposed weight, gn_backward dense; it stops at the lowest layer that
+        learns."""
+
+        @staticmethod
+        def forward(ctx, net, src, ref, *params):
+            x = net._input(f32c(src.detach()), f32c(ref.detach()))
+            pooled, (ys, affs, stats, ext, pw) = net._prepool_hip(x, keep=True)
+            ctx.net = net
+            ctx.save_for_backward(x, ext, pw, *ys, *affs, *stats, *params)
+            return pooled
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, dpooled):
+            from ._train import channel_stats, sum_clouds, wgrad
+            net = ctx.net
+            layers = net._layers()
+            L = len(layers)
+            saved = list(ctx.saved_tensors)
+            x, ext, pw = saved[:3]
+            ys, affs, stats, params = saved[3:L + 2], saved[L + 2:3 * L + 2], saved[3 * L + 2:4 * L + 2], saved[4 * L + 2:]
+            needs = ctx.needs_input_grad[3:]
+            grads = [None] * len(params)
+            slot = {id(p): j for j, p in enumerate(net._parameters_in_order())}
+
+            def learns_below(i):
+                """does the convolution of layer i, or anything underneath, need a gradient"""
+                upto = [p for c, n in layers[:i] for p in (c.weight, c.bias, n.weight, n.bias)] + [layers[i][0].weight, layers[i][0].bias]
+                return any(needs[slot[id(p)]] for p in upto)
+
+            with on_device_of(x):
+                conv, norm = layers[-1]
+                a5, s5 = affs[-2], affs[-1]
+                g = f32c(dpooled) * (net._pooled(a5, s5, ext) > 0)
+                jg, jt = slot[id(norm.weight)], slot[id(norm.bias)]
+                dz, grads[jg], grads[jt] = gn_gpool_backward(
+                    ys[-1] if L > 1 else x, affs[-4] if L > 1 else None, affs[-3] if L > 1 else None, params[slot[id(conv.weight)]],
+                    params[slot[id(conv.bias)]], g, ext, pw, stats[-1], params[jg], norm.num_groups, want_dz=learns_below(L - 1),
+                    want_gamma=needs[jg], want_beta=needs[jt])
+                for i in range(L - 1, -1, -1):
+                    if dz is None:
+                        break
+                    conv, _ = layers[i]
+                    jw, jb = slot[id(conv.weight)], slot[id(conv.bias)]
+                    if needs[jw]:
+                        u = x if i == 0 else gn_relu(ys[i - 1], affs[2 * i - 2], affs[2 * i - 1])
+                        grads[jw] = wgrad(dz, u).view_as(conv.weight)
+                        del u                              # back to the allocator before du and dz of the layer below are made
+                    if needs[jb]:
+                        grads[jb] = sum_clouds(channel_stats(dz))[:, 0].float()
+                    if i == 0 or not (learns_below(i - 1) or needs[slot[id(layers[i - 1][1].weight)]]
+                                      or needs[slot[id(layers[i - 1][1].bias)]]):
+                        break                              # the first layer, or nothing underneath learns
+                    w = f32c(params[jw]).view(conv.out_channels, conv.in_channels)
+                    du = gn_conv(dz, None, None, w.t().contiguous(), None)[0]
+                    del dz                                 # layer 5's is the one [B,1024,P] tensor: gone before the next is made
+                    norm = layers[i - 1][1]
+                    jg, jt = slot[id(norm.weight)], slot[id(norm.bias)]
+                    dz, grads[jg], grads[jt] = gn_backward(du, ys[i - 1], affs[2 * i - 2], affs[2 * i - 1], stats[i - 1], params[jg],
+                                                           norm.num_groups, want_gamma=needs[jg], want_beta=needs[jt])
+                    del du
+            return (None, None, None, *grads)
+
     def forward(self, x):
-        """x = [src [B,J,3], ref [B,K,3]] -> beta [B], alpha [B]"""
+        """x = [src [B,J,3], ref [B,K,3]] -> beta [B], alpha [B]: the pre-pool stack on _Train where trains_on_hip holds, the op
+        sequence else (the eval HIP route is fused_forward, the caller's choice)"""
+        if self.trains_on_hip(x[0], x[1]):
+            with on_device_of(x[0]):
+                return self._head(self._Train.apply(self, x[0], x[1], *self._parameters_in_order()))
         src = F.pad(x[0], (0, 1), mode='constant', value=0)
         ref = F.pad(x[1], (0, 1), mode='constant', value=1)
         feat = self.prepool(torch.cat([src, ref], dim=1).permute(0, 2, 1))
@@ -340,7 +559,9 @@ class RPMNet(nn.Module):
         cur, cur_n = xyz_s, norm_s
         transforms, gammas, perms, weighted, betas, alphas = [], [], [], [], [], []
         for _ in range(max_iterations):
-            self.beta, self.alpha = self.weights_net([cur, xyz_t])
+            wn = self.weights_net
+            hip_params = hasattr(wn, "fused_takes") and wn.fused_takes(cur, xyz_t)
+            self.beta, self.alpha = wn.fused_forward([cur, xyz_t]) if hip_params else wn([cur, xyz_t])
             self.feat_source = fx.fused_features(cur, cur_n)
             dist = _device_square_distance(self.feat_source, self.feat_template)
             self.affinity = self.compute_affinity(self.beta, dist, alpha=self.alpha)

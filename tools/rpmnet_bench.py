@@ -2,6 +2,8 @@
 against the op-sequence route of the same build, and the kernels of rpmnet.hip alone against the torch ops they replace
 (l3d_gn_affine is not timed separately: it runs behind every l3d_gn_conv of the pre-pool stack).  The two sides of each pair run
 interleaved, round by round, so that clock and thermal drift hits both alike; medians over the rounds.
+param_net_* and fused_iters*_param_*: ParameterPredictionNet alone (no_grad) and the whole fused forward with rpmnet.PARAM_HIP on and
+off, everything else fused on both sides; [median, min, max] over the rounds.
 
     python tools/rpmnet_bench.py [--batch 32] [--points 1024] [--rounds 10]
 Prints one JSON line."""
@@ -98,6 +100,34 @@ def main():
     for name in cases:
         line[name + "_ms_fused"] = med(res[name][True])
         line[name + "_ms_op_sequence"] = med(res[name][False])
+
+    # PARAM_HIP on / off, FUSED on on both sides
+    wn, moved = net.weights_net, xyz @ R.t() + 0.1
+
+    def param_net():
+        if rpmnet.PARAM_HIP:
+            wn.fused_forward([moved, xyz])
+        else:
+            wn([moved, xyz])
+    ab = {"param_net": param_net}
+    ab.update({f"fused_iters{n}_param": (lambda n=n: net(template, source, n)) for n in a.iterations})
+    sides = {"hip": True, "torch": False}
+    ms = {name: {k: [] for k in sides} for name in ab}
+    with torch.no_grad():
+        for name, fn in ab.items():
+            for rounds in (1, a.rounds):                  # one warm-up round, then the timed ones
+                for r in range(rounds):
+                    for k, on in sides.items():
+                        rpmnet.PARAM_HIP = on
+                        try:
+                            t = timed(lambda fused: fn(), True, a.reps)
+                        finally:
+                            rpmnet.PARAM_HIP = True
+                        if rounds > 1:
+                            ms[name][k].append(t)
+    for name in ab:
+        for k in sides:
+            line[f"{name}_ms_{k}"] = [med(ms[name][k]), round(min(ms[name][k]), 4), round(max(ms[name][k]), 4)]
     print(json.dumps(line))
 
 

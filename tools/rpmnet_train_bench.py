@@ -17,6 +17,10 @@ autograd -- what every build before this route ran):
                                  pass.  Bytes: log_alpha once per pass, the dense cotangent and dist where a pass reads them, d_out
                split             forward + backward of each other part of an iteration alone at the step's shapes:
                                  ParameterPredictionNet, the feature distance, the weighted Kabsch step
+  param      ParameterPredictionNet's pre-pool stack on its HIP route against torch autograd of the same build (rpmnet.PARAM_HIP =
+             False, every other route on on both sides), [median, min, max] over the rounds:
+               param_net_*       forward + backward of the network alone at J = K = points
+               step_param_*      the whole step with PARAM_HIP on and off
 
 The two sides of each pair run interleaved, round by round, so that clock and thermal drift hits both alike; medians over the
 rounds.  Peak memory is torch.cuda.max_memory_allocated over one warm round of each side, above what was allocated before it.
@@ -59,20 +63,21 @@ def peak(fn, hip):
     return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
 
 
-def with_match(fn, on):
-    """fn with rpmnet.MATCH_HIP = on"""
+def with_switch(fn, switch, on):
+    """fn with rpmnet.<switch> = on"""
     def run():
-        prev, rpmnet.MATCH_HIP = rpmnet.MATCH_HIP, on
+        prev = getattr(rpmnet, switch)
+        setattr(rpmnet, switch, on)
         try:
             fn()
         finally:
-            rpmnet.MATCH_HIP = prev
+            setattr(rpmnet, switch, prev)
     return run
 
 
-def pair(line, name, fn, rounds):
-    """ms (median, min, max) and peak of fn with MATCH_HIP on and off, interleaved round by round"""
-    sides = {"hip": with_match(fn, True), "torch": with_match(fn, False)}
+def pair(line, name, fn, rounds, switch="MATCH_HIP"):
+    """ms (median, min, max) and peak of fn with the switch (MATCH_HIP, PARAM_HIP) on and off, interleaved round by round"""
+    sides = {"hip": with_switch(fn, switch, True), "torch": with_switch(fn, switch, False)}
     ms = {k: [] for k in sides}
     for f in sides.values():
         timed(f, True)
@@ -161,6 +166,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--no-kernels", action="store_true")
     ap.add_argument("--no-matching", action="store_true")
+    ap.add_argument("--no-param", action="store_true")
+    ap.add_argument("--no-routes", action="store_true", help="skip the TRAIN_HIP on / off pairs (features, step)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     N = a.points
@@ -192,7 +199,7 @@ def main():
             opt.step()
 
         line = {"batch": B, "points": N, "neighbors": fx.n_sample, "rounds": a.rounds}
-        for name, fn in (("features", features), ("step", step)):
+        for name, fn in (() if a.no_routes else (("features", features), ("step", step))):
             ms = {True: [], False: []}
             for hip in (True, False):
                 timed(fn, hip)                            # warm-up: caches, lazy module loads, the allocator's blocks
@@ -203,6 +210,16 @@ def main():
             line[name + "_ms_op_sequence"] = round(statistics.median(ms[False]), 3)
             line[name + "_peak_mib_hip"] = round(peak(fn, True), 1)
             line[name + "_peak_mib_op_sequence"] = round(peak(fn, False), 1)
+        if not a.no_param:
+            moved_src = xyz @ R.t() + 0.1
+
+            def param_net():
+                net.zero_grad(set_to_none=True)
+                beta, alpha = net.weights_net([moved_src, xyz])
+                (beta.sum() + alpha.sum()).backward()
+
+            pair(line, "param_net", param_net, a.rounds, "PARAM_HIP")
+            pair(line, "step_param", step, a.rounds, "PARAM_HIP")
         if not a.no_matching:
             dist0 = torch.rand(B, N, N, device=dev) * 2
             feat_s = torch.nn.functional.normalize(torch.randn(B, N, fx.postpool[6].out_channels, device=dev), dim=-1)
