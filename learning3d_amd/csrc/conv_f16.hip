@@ -34,6 +34,9 @@
 // DMA data is never waited for (latency hidden), but ISSUING five 1 KB DMA instructions in one block behind the barrier cost
 // every wave ~600 cycles (the CU's vector-memory path takes them at 16 cycles apiece and all eight waves queue at once):
 // spread out, 99 -> 96 us.  The two epilogues (one per tile round; 134 MB) are exposed, ~17 us each.
+// conv5's own form (two weight planes, fp32 y, Cin / 16 >= 5) is conv_f16_tail_kernel below: four stages, and the last three K chunks
+// taken MFMA tile by MFMA tile so that each tile's stores leave under the other tiles' MFMAs -- the same bits, each epilogue ~2.5 us
+// shorter (LABLOG R26.1).  Shorter K and every other output mode stay on conv_f16_kernel.
 // Measured, not kept (LABLOG R2.3): next-chunk x fragments read during this chunk's MFMAs (spills: 112 us); four-wave
 // 128 x 256 workgroups, two per CU, which do hide the epilogue (99 us); those with W fragments straight from L2 (110 us);
 // all 14 reads ahead of the first MFMA (105 us); first-product fragments read across the barrier (105 us); LDS bank
@@ -42,6 +45,7 @@
 #include "common.h"
 #include "split_bf16.h"          // f32x4 / f32x16 typedefs
 #include "split_f16.h"
+#include "../../include/ext/l3d_conv_f16_route.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
@@ -52,6 +56,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 #define CF_STAGE (CF_WBYTES + CF_XBYTES)
 #define CF_NSTAGE 3
 #define CF_LDS (CF_NSTAGE * CF_STAGE)
+#define CF_TAIL L3D_CONV_F16_TAIL_CHUNKS     // K chunks of the plain two-plane form's tile-major tail (conv_f16_tail_kernel)
 
 typedef __attribute__((address_space(3))) void *cf_lds_ptr_t;
 typedef const __attribute__((address_space(1))) void *cf_gbl_ptr_t;
@@ -705,6 +710,198 @@ __global__ __launch_bounds__(512) void conv_f16_kernel(const uint4 *__restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The plain two-plane form (conv_f16_kernel<false, false, false, 2>: wide tile, fp32 y and nothing else -- DGCNN's conv5) with a
+// TILE-MAJOR TAIL, for Cin / 16 >= CF_TAIL + 2.  A kernel of its own, so that conv_f16_kernel's instantiations keep their code.
+// In the chunk loop every K chunk updates all eight MFMA tiles of a wave, so all 128 accumulators become final together in the last
+// chunk and every store stands in the open with the matrix pipe idle (per tile: fill 2.3, main loop 33.9, epilogue 8.8 us -- R6.1).
+// Here the last CF_TAIL = 3 chunks leave the chunk loop and run unrolled and barrier-free, tile by tile: for MFMA tile (a, c) chunks
+// K-3, K-2, K-1 with their three products each, then that tile's 16 accumulators through scale / shift / activation and out as
+// stores while the other tiles' MFMAs still issue: tile j is final after 9 (j + 1) of the tail's 72 MFMAs, and the store path (16 B per
+// clock and CU, the epilogue's limit) starts ~3 us earlier per workgroup tile.  Per accumulator the order of accumulation is the loop's
+// (chunks ascend; M h, H m, H h within a chunk) and the epilogue's expression is the loop form's: the output bits are the same.
+//   * FOUR stages of 32 KB, so that chunks K-3 .. K-1 are resident together.  Stage (kc + 3) % 4 is free during chunk kc (last read
+//     in chunk kc - 1, behind this chunk's barrier), so chunk K-5 issues chunk K-2 beside its usual K-3 and chunk K-4 issues chunk
+//     K-1: the tail's last chunk has a whole chunk's time to land, as every chunk of the loop has.  Hence K >= CF_TAIL + 2 chunks.
+//   * one s_waitcnt vmcnt(0) + barrier at the tail's entry instead of three; behind it nothing is in flight and the stores' own
+//     vmcnt traffic meets no DMA (the tail has no vmcnt wait at all).
+//   * the per-row constants (scale 2^-S, shift) of the workgroup's 256 rows parked in LDS behind the stages at the kernel's start
+//     (2 KB; LDS 130 KB of 160): the tail reads them per tile with ds_read_b128 -- global loads between the stores would have
+//     to wait for the stores in front of them.
+// 198 VGPRs, no scratch (the loop form: 204).  Measured: LABLOG R26.1.
+// ---------------------------------------------------------------------------------------------
+#define CFT_STAGE (4 * CF_TM * 16 + 4 * CF_TN * 16)                      // H, M (2 octets x 256 rows) | h, m: 32 KB
+#define CFT_LDS (4 * CFT_STAGE + 2 * CF_TM * (int)sizeof(float))           // four stages | scale 2^-S [256] | shift [256]
+__global__ __launch_bounds__(512) void conv_f16_tail_kernel(const uint4 *__restrict__ xh, const uint4 *__restrict__ xm,
+                                                            const uint4 *__restrict__ wH, const uint4 *__restrict__ wM,
+                                                            const float *__restrict__ winv, const float *__restrict__ xinv,
+                                                            const float *__restrict__ scale, const float *__restrict__ shift,
+                                                            int shift_bstride, int Bn, int Cin, int Cout, int N, int relu, float *__restrict__ y)
+{
+    constexpr int WR = CF_TM * 16, XR = CF_TN * 16, WBYTES = 4 * WR, STAGE = CFT_STAGE, NPIECE = 4, T = CF_TAIL;
+    static_assert(CF_TM == 256 && CF_TN == 256 && T == 3, "32 pieces of 64 rows per chunk, four per wave; stage arithmetic mod 4");
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wm = wave & 3, wn = wave >> 2;
+    CFM(0)
+#ifdef CF_TIMELINE
+    if (t == 0) { unsigned id; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(id)); g_cf_timeline[(size_t)blockIdx.x * 8 + 7] = id; }
+#endif
+    // tile order: conv_f16_kernel's (the Cout tiles of one point tile on one XCD)
+    int pt, ct;
+    {
+        const int nct = Cout / CF_TM, npt = Bn * (N / CF_TN), L = blockIdx.x;
+        if (npt % 8 == 0) {
+            const int xcd = L & 7, slot = L >> 3;
+            ct = slot % nct;
+            pt = (slot / nct) * 8 + xcd;
+        } else {
+            ct = L % nct;
+            pt = L / nct;
+        }
+    }
+    const int ntn = N / CF_TN;
+    const int n0 = (pt % ntn) * CF_TN, co0 = ct * CF_TM, b = pt / ntn;
+    const int nk = Cin / 16;                         // >= T + 2 (cf_launch)
+    const size_t BN = (size_t)Bn * N;
+
+    // DMA pieces of 64 rows (1 KB): W 4 regions (H, M x 2 octets) x 4, x 4 regions (h, m x 2 octets) x 4 -- 32 per chunk, 4 per wave
+    const uint4 *src[NPIECE];
+    size_t stride[NPIECE];
+    int dst[NPIECE];
+#pragma unroll
+    for (int i = 0; i < NPIECE; i++) {
+        const int q = wave * NPIECE + i, reg = (q & 15) >> 2, p = reg >> 1, kg = reg & 1, quarter = q & 3;
+        if (q < 16) {
+            src[i] = (p == 0 ? wH : wM) + (size_t)kg * Cout + co0 + quarter * 64 + lane;
+            stride[i] = 2 * (size_t)Cout;
+            dst[i] = reg * WR + quarter * 1024;
+        } else {
+            src[i] = (p == 0 ? xh : xm) + (size_t)kg * BN + (size_t)b * N + n0 + quarter * 64 + lane;
+            stride[i] = 2 * BN;
+            dst[i] = WBYTES + reg * XR + quarter * 1024;
+        }
+    }
+    auto issue_one = [&](int stage, int i) {
+        __builtin_amdgcn_global_load_lds((cf_gbl_ptr_t)src[i], (cf_lds_ptr_t)(lds + stage * STAGE + dst[i]), 16, 0, 0);
+        src[i] += stride[i];
+    };
+
+    f32x16 acc[2][4];
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[a][c][r] = 0.f;
+
+    const int kgl = lane >> 5;
+    const int a_off = kgl * WR + (wm * 64 + (lane & 31)) * 16;                       // + a*512 + p*2*WR
+    const int b_off = WBYTES + kgl * XR + (wn * 128 + (lane & 31)) * 16;             // + c*512 + p*2*XR
+
+#pragma unroll
+    for (int i = 0; i < NPIECE; i++) issue_one(0, i);
+#pragma unroll
+    for (int i = 0; i < NPIECE; i++) issue_one(1, i);
+    // the rows' constants -> LDS (waves 0 .. 3; read behind the tail's barrier)
+    float *csc = (float *)(lds + 4 * STAGE), *csh = csc + CF_TM;
+    if (t < CF_TM) {
+        csc[t] = (scale ? scale[co0 + t] : 1.f) * winv[4 + co0 + t];                 // 2^-S_co: the weight image's per-row exponents
+        csh[t] = shift ? shift[(size_t)b * shift_bstride + co0 + t] : 0.f;
+    }
+    const float xinv0 = *xinv;                       // 2^-T
+    for (int kc = 0; kc < nk - T; kc++) {
+        // this wave's pieces of chunk kc have landed; behind them in flight: chunk kc+1 (4 pieces), in chunk nk-4 chunks nk-3 and nk-2 (8)
+        const bool last = kc == nk - T - 1, prev = kc == nk - T - 2;
+        if (last) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                // ... and everybody else's; stages (kc+2)%4 and (kc+3)%4 were last read in chunks kc-2 and kc-1
+#ifdef CF_TIMELINE
+        if (kc == 0) CFM(1)
+#endif
+        const int ust = last ? ((kc + 3) & 3) : ((kc + 2) & 3), est = (kc + 3) & 3;
+        const unsigned char *base = lds + (kc & 3) * STAGE;
+        f16x8 A[2][2], Bf[4][2];
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+#pragma unroll
+            for (int c = 0; c < 4; c++) Bf[c][p] = *(const f16x8 *)(base + b_off + c * 512 + p * 2 * XR);
+#pragma unroll
+        for (int p = 1; p >= 0; p--)
+#pragma unroll
+            for (int a = 0; a < 2; a++) A[a][p] = *(const f16x8 *)(base + a_off + a * 512 + p * 2 * WR);
+        // three products, smallest first: M h, H m, H h; the DMA instructions spread between them as in conv_f16_kernel
+#pragma unroll
+        for (int n = 0; n < 24; n++) {
+            const int prod = n >> 3, a = (n >> 2) & 1, c = n & 3;
+            acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[a][prod == 0 ? 1 : 0], Bf[c][prod == 1 ? 1 : 0], acc[a][c], 0, 0, 0);
+            // the usual piece behind MFMA 3, 9, 15, 21 (chunk kc+2; in chunk nk-4: chunk nk-1); in chunk nk-5 chunk nk-2's behind 5, 11, 17, 23
+            if (n % 6 == 3) {
+                __builtin_amdgcn_sched_barrier(0);
+                issue_one(ust, n / 6);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (n % 6 == 5) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (prev) issue_one(est, n / 6);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    CFM(2)
+    // ---- the tail: D[co = 32a + (r&3) + 8(r>>2) + 4(lane>>5)][n = 32c + (lane&31)], y = ((acc (scale 2^-S_co)) 2^-T) + shift as in the loop form.
+    // Addresses: a wave-uniform row pointer + one lane offset (the wave index is uniform, which the compiler cannot see)
+    const int wmu = __builtin_amdgcn_readfirstlane(wm), wnu = __builtin_amdgcn_readfirstlane(wn);
+    float *yu = y + ((size_t)b * Cout + co0 + wmu * 64) * N + n0 + wnu * 128;
+    const unsigned voff = (unsigned)(4 * kgl) * (unsigned)N + (unsigned)(lane & 31);
+    const unsigned char *cb[T];
+#pragma unroll
+    for (int j = 0; j < T; j++) cb[j] = lds + ((nk - T + j) & 3) * STAGE;
+    const float *lsc = csc + wm * 64 + 4 * kgl, *lsh = csh + wm * 64 + 4 * kgl;
+#pragma unroll
+    for (int a = 0; a < 2; a++) {
+        f16x8 A[T][2];
+#pragma unroll
+        for (int j = 0; j < T; j++)
+#pragma unroll
+            for (int p = 0; p < 2; p++) A[j][p] = *(const f16x8 *)(cb[j] + a_off + a * 512 + p * 2 * WR);
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            f16x8 Bf[T][2];
+#pragma unroll
+            for (int j = 0; j < T; j++)
+#pragma unroll
+                for (int p = 0; p < 2; p++) Bf[j][p] = *(const f16x8 *)(cb[j] + b_off + c * 512 + p * 2 * XR);
+#pragma unroll
+            for (int j = 0; j < T; j++) {            // M h, H m, H h
+                acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[j][1], Bf[j][0], acc[a][c], 0, 0, 0);
+                acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[j][0], Bf[j][1], acc[a][c], 0, 0, 0);
+                acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[j][0], Bf[j][0], acc[a][c], 0, 0, 0);
+            }
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const f32x4 sc4 = *(const f32x4 *)(lsc + a * 32 + 8 * g), sh4 = *(const f32x4 *)(lsh + a * 32 + 8 * g);
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    float v = acc[a][c][4 * g + u] * sc4[u] * xinv0 + sh4[u];
+                    if (relu) v = l3d_act(v, relu);
+                    __builtin_nontemporal_store(v, yu + (size_t)(a * 32 + u + 8 * g) * N + c * 32 + voff);      // nontemporal: see conv_f16_kernel's epilogue
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);       // tile by tile: the next tile's reads and MFMAs stay behind this tile's stores in program order
+        }
+    }
+#ifdef CF_TIMELINE
+    CFM(3)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    CFM(4)
+    __syncthreads();
+    CFM(5)
+#endif
+}
+
 // Sizes of the plane images (common.h: l3d_f16_plane_bytes / l3d_f16_act_bytes / l3d_conv_f16_weight_bytes), one exported spelling:
 // kind 0 = ONE fp16 plane of a [rows][cols] matrix in the tiled layout; 1 = an activation image (h | m' planes + 16 bytes:
 // 2^-T, scratch); 2 = a weight image of [rows = Cout][cols = Cin] (H | Hs | M planes + 16 bytes: 2^-S, |w| maximum, row-sum maximum)
@@ -790,6 +987,9 @@ extern "C" int l3d_split_f16_operand(const float *x, long rows, int C, long row_
     return l3d_check_launch();
 }
 
+// the plain two-plane form (fp32 y, no residual / maxima / image): the tile-major tail needs its TAIL chunks and two in front of them
+static bool cf_tail_route(int Cin) { return Cin / 16 >= CF_TAIL + 2; }
+
 // x_act: an activation image (l3d_f16_act_bytes), w_planes: a weight image (l3d_conv_f16_weight_bytes)
 static int cf_launch(const void *x_planes, const void *w_planes, const float *scale, const float *shift, int shift_bstride, int B,
                      int Cin, int Cout, int N, int relu, float *y, void *out_img, const float *obs, float *ypool, int pool,
@@ -838,6 +1038,12 @@ static int cf_launch(const void *x_planes, const void *w_planes, const float *sc
     }
     if (two_plane) {
         if (narrow || group || amax_out || ypool || out_img || !y) return L3D_ERR_UNSUPPORTED;
+        if (cf_tail_route(Cin)) {                    // enough K chunks for the tile-major tail: same grid, same bits
+            hipLaunchKernelGGL(conv_f16_tail_kernel, grid, block, CFT_LDS, st, (const uint4 *)xp, (const uint4 *)(xp + xpb), (const uint4 *)wp,
+                               (const uint4 *)(wp + 2 * wpb), (const float *)(wp + 3 * wpb), (const float *)(xp + 2 * xpb), scale, shift,
+                               shift_bstride, B, Cin, Cout, N, relu, y);
+            return l3d_check_launch();
+        }
         hipLaunchKernelGGL((conv_f16_kernel<false, false, false, 2>), grid, block, 3 * (4 * CF_TM * 16 + 4 * CF_TN * 16), st, CF_ARGS);
         return l3d_check_launch();
     }
@@ -866,7 +1072,8 @@ static int cf_launch(const void *x_planes, const void *w_planes, const float *sc
 //             hands the attention kernel its operand maxima
 // flags: 1 (L3D_CONV_F16_TWO_PLANE) -- the input image's residual plane is UNSCALED (m = f16(X - h), written by
 //        l3d_edgeconv_forward_f16b with out_mode 2, l3d_layernorm_planes / l3d_attention_forward_f16b / this kernel when asked): the Hs
-//        plane of the weight image is not read (wide tile; y, y + residual, y + amax_out, or out_img with flag 2).
+//        plane of the weight image is not read (wide tile; y, y + residual, y + amax_out, or out_img with flag 2).  With y alone and
+//        Cin >= 80 it runs conv_f16_tail_kernel (l3d_conv_f16_route tells which form a call takes; both give the same bits).
 //        2 (L3D_CONV_F16_OUT_UNSCALED) -- out_img gets an unscaled residual plane as well (needs flag 1).
 //        4 (L3D_CONV_F16_SHIFT_N) -- shift [N] is indexed by the output column (needs flag 1; y only): with w_planes = the rows of a batch
 //        (l3d_split_f16_operand kind 1) and x_planes = a layer's [Cout][Cin] matrix (kind 0), y [1][rows][Cout] = x W^T + b.
@@ -881,6 +1088,17 @@ extern "C" int l3d_pointwise_conv_f16(const void *x_planes, const void *w_planes
     if (y && (out_img || ypool)) return L3D_ERR_UNSUPPORTED;                  // the epilogue writes fp32 rows OR planes / pooled maxima
     return cf_launch(x_planes, w_planes, scale, shift, shift_bstride, B, Cin, Cout, N, relu, y, out_img, obs, ypool, pool,
                      (unsigned *)amax_out, amax_cdiv, (hipStream_t)stream, (flags & 1) != 0, residual, (flags & 2) != 0, (flags & 4) != 0);
+}
+
+// Which form of the kernel an l3d_pointwise_conv_f16 call with these sizes and flags runs when it asks for y alone (no residual, maxima,
+// image or pool): L3D_CONV_F16_ROUTE_TAIL (the tile-major tail), L3D_CONV_F16_ROUTE_LOOP, or L3D_ERR_UNSUPPORTED for sizes it refuses.
+extern "C" int l3d_conv_f16_route(int Cin, int Cout, int N, int flags)
+{
+    L3D_REQUIRE(Cin > 0 && Cout > 0 && N > 0 && (flags & ~7) == 0);
+    const bool narrow = Cout % CF_TM != 0;
+    if (Cout % (narrow ? 128 : CF_TM) || N % (narrow ? 512 : CF_TN) || Cin % 16 || (flags & 2) || ((flags & 4) && !(flags & 1)) || ((flags & 1) && narrow))
+        return L3D_ERR_UNSUPPORTED;
+    return (flags == 1 && cf_tail_route(Cin)) ? L3D_CONV_F16_ROUTE_TAIL : L3D_CONV_F16_ROUTE_LOOP;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -8,7 +8,7 @@ import sys
 
 
 def short(n):
-    for key in ("knn_mfma", "edgeconv_f16b", "conv_f16_kernel", "chamfer_fwd", "chamfer_loss", "conv5_persist", "mfma_sustained"):
+    for key in ("knn_mfma", "edgeconv_f16b", "conv_f16_kernel", "conv_f16_tail_kernel", "chamfer_fwd", "chamfer_loss", "conv5_persist", "mfma_sustained"):
         if key in n:
             return key
     return n.split("(")[0][-40:]
