@@ -637,6 +637,17 @@ int l3d_sa_mlp3_fused(const float *xyz, const float *new_xyz, const float *feat,
 int l3d_bmm_f32(const float *A, const long *a_strides, const float *B, const long *b_strides, float *C, const long *c_strides,
                 int nb1, int nb2, int M, int N, int K, float alpha, int flags, const float *bias, int parts, float *workspace,
                 l3d_stream_t stream);
+/* Which form of the kernel an l3d_bmm_f32 call with these operands, sizes and `parts` runs (host arithmetic; launches nothing):
+ * bits 0-1 the 32-column MFMA tiles per wave (1: 128 x 64 workgroup tiles, 2: 128 x 128), bits 2-3 the fetch form of A and bits 4-5
+ * that of B (1: 16-byte loads along k, 2: 16-byte loads along the rows, 0: scalar loads), L3D_BMM_ROUTE_REMAPPED when the grid's tiles
+ * are reordered so that a row tile's column tiles share an XCD (row tiles % 8 == 0).  L3D_ERR_INVALID_ARG / L3D_ERR_UNSUPPORTED for
+ * the pointers, strides and sizes l3d_bmm_f32 answers with them. */
+#define L3D_BMM_ROUTE_YT_MASK 3
+#define L3D_BMM_ROUTE_A_SHIFT 2
+#define L3D_BMM_ROUTE_B_SHIFT 4
+#define L3D_BMM_ROUTE_REMAPPED 64
+int l3d_bmm_f32_route(const float *A, const long *a_strides, const float *B, const long *b_strides, int nb1, int nb2, int M, int N,
+                      int K, int parts);
 int l3d_softmax_rows(const float *x, const float *dp, long rows, int cols, float scale, float *y, l3d_stream_t stream);
 size_t l3d_colsum_rows_workspace_bytes(long rows, int cols);
 int l3d_colsum_rows(const float *x, long rows, int cols, long row_stride, void *workspace, float *out, l3d_stream_t stream);

@@ -269,6 +269,32 @@ static int bm_mode(const float *p, const long s[4], int R, int K)
     return 0;
 }
 
+// What a call runs: the instantiation (YT, the two fetch forms), its grid, and whether bmm_f32_kernel reorders that grid's tiles.
+// l3d_bmm_f32 launches from this and l3d_bmm_f32_route reports it, so the two cannot disagree.
+struct BmRoute {
+    int yt, am, bm;
+    bool remap;
+    dim3 grid;
+};
+
+static int bm_route(const float *A, const long *a_strides, const float *B, const long *b_strides, int nb1, int nb2, int M, int N, int K,
+                    int parts, BmRoute *r)
+{
+    L3D_REQUIRE(A && B && a_strides && b_strides && nb1 > 0 && nb2 > 0 && M > 0 && N > 0 && K > 0 && parts >= 1);
+    const long nz = (long)nb1 * nb2 * parts;
+    if (nz > 65535 || l3d_divup(M, BM_T) > 65535) return L3D_ERR_UNSUPPORTED;
+    // B as a [N rows x K] operand: "along k" is its row stride, "along rows" its column stride
+    const long bsw[4] = {b_strides[0], b_strides[1], b_strides[3], b_strides[2]};
+    r->am = bm_mode(A, a_strides, M, K);
+    r->bm = bm_mode(B, bsw, N, K);
+    // 128 x 128 tiles when they fill the chip twice over, 128 x 64 otherwise
+    const long wide = (long)l3d_divup(N, 128) * l3d_divup(M, BM_T) * nz;
+    r->yt = (wide >= 512 && N > 64) ? 2 : 1;
+    r->grid = dim3((unsigned)l3d_divup(N, r->yt == 2 ? 128 : 64), (unsigned)l3d_divup(M, BM_T), (unsigned)nz);
+    r->remap = (r->grid.y & 7) == 0;              // the kernel's own test on gridDim.y (its tile order)
+    return L3D_OK;
+}
+
 // C[i][j] = act(alpha A[i][j] B[i][j] + bias) (+ C[i][j]),  A [M x K], B [K x N], C [M x N], i < nb1, j < nb2;
 // *_strides = {batch1, batch2, row, column} in elements (a transposed operand is its strides swapped; a broadcast one has batch
 // strides 0).  flags: 1 accumulate into C, 2 ReLU, 4 bias[n], 8 bias[m].  parts > 1: split K into `parts` ranges whose partial
@@ -280,18 +306,15 @@ extern "C" int l3d_bmm_f32(const float *A, const long *a_strides, const float *B
 {
     L3D_REQUIRE(A && B && C && a_strides && b_strides && c_strides && nb1 > 0 && nb2 > 0 && M > 0 && N > 0 && K > 0 &&
                 (flags & ~15) == 0 && (!(flags & 12) || bias) && parts >= 1 && (parts == 1 || workspace));
-    const long nz = (long)nb1 * nb2 * parts;
-    if (nz > 65535 || l3d_divup(M, BM_T) > 65535) return L3D_ERR_UNSUPPORTED;
+    BmRoute route;
+    const int status = bm_route(A, a_strides, B, b_strides, nb1, nb2, M, N, K, parts, &route);
+    if (status != L3D_OK) return status;
     hipStream_t st = (hipStream_t)stream;
     BmOperand a{A, a_strides[0], a_strides[1], a_strides[2], a_strides[3], 0};
     BmOperand b{B, b_strides[0], b_strides[1], b_strides[2], b_strides[3], 0};
-    // B as a [N rows x K] operand: "along k" is its row stride, "along rows" its column stride
-    const long bsw[4] = {b_strides[0], b_strides[1], b_strides[3], b_strides[2]};
-    const int am = bm_mode(A, a_strides, M, K), bm = bm_mode(B, bsw, N, K);
-    // 128 x 128 tiles when they fill the chip twice over, 128 x 64 otherwise
-    const long wide = (long)l3d_divup(N, 128) * l3d_divup(M, BM_T) * nz;
-    const bool yt2 = wide >= 512 && N > 64;
-    dim3 grid((unsigned)l3d_divup(N, yt2 ? 128 : 64), (unsigned)l3d_divup(M, BM_T), (unsigned)nz);
+    const int am = route.am, bm = route.bm;
+    const bool yt2 = route.yt == 2;
+    const dim3 grid = route.grid;
 #define BM_LAUNCH(YT, AM, BMD)                                                                                                             \
     hipLaunchKernelGGL((bmm_f32_kernel<YT, AM, BMD>), grid, dim3(256), 0, st, a, b, C, c_strides[0], c_strides[1], c_strides[2], c_strides[3], \
                        nb2, M, N, K, alpha, flags, bias, parts, workspace)
@@ -310,6 +333,18 @@ extern "C" int l3d_bmm_f32(const float *A, const long *a_strides, const float *B
                            c_strides[2], c_strides[3], nb2, M, N, alpha, flags, bias);
     }
     return l3d_check_launch();
+}
+
+// Which kernel an l3d_bmm_f32 call with these operands, sizes and `parts` runs, and in which tile order: YT | A's fetch form << 2 | B's
+// << 4 | L3D_BMM_ROUTE_REMAPPED when the kernel reorders the grid's tiles.  The statuses l3d_bmm_f32 gives for the same arguments
+// otherwise.  Launches nothing.
+extern "C" int l3d_bmm_f32_route(const float *A, const long *a_strides, const float *B, const long *b_strides, int nb1, int nb2, int M,
+                                 int N, int K, int parts)
+{
+    BmRoute route;
+    const int status = bm_route(A, a_strides, B, b_strides, nb1, nb2, M, N, K, parts, &route);
+    if (status != L3D_OK) return status;
+    return route.yt | route.am << L3D_BMM_ROUTE_A_SHIFT | route.bm << L3D_BMM_ROUTE_B_SHIFT | (route.remap ? L3D_BMM_ROUTE_REMAPPED : 0);
 }
 
 // ---------------------------------------------------------------------------------------------

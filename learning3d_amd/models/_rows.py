@@ -12,7 +12,8 @@ import os
 
 import torch
 
-from .._lib import L3D_CONV_F16_SHIFT_N, L3D_CONV_F16_TWO_PLANE, call, f32c, lib, on_device_of
+from .._lib import (L3D_BMM_ROUTE_A_SHIFT, L3D_BMM_ROUTE_B_SHIFT, L3D_BMM_ROUTE_REMAPPED, L3D_BMM_ROUTE_YT_MASK, L3D_CONV_F16_SHIFT_N,
+                    L3D_CONV_F16_TWO_PLANE, call, check, f32c, lib, on_device_of, ptr)
 
 _ONES = {}
 
@@ -39,9 +40,8 @@ def _st(t):
     return (C.c_long * 4)(*[int(s) for s in t.stride()])
 
 
-def bmm(a, b, alpha=1.0, out=None, relu=False, bias=None, bias_axis="n", accumulate=False, parts=1):
-    """a [..., M, K] @ b [..., K, N] (same number of axes, up to two batch axes, any strides -- transposed, sliced or expanded
-    views are read in place) -> act(alpha a b + bias) [..., M, N] fp32.  out: a tensor (any strides) to write / accumulate into."""
+def _bmm_operands(a, b):
+    """the operands of a [..., M, K] @ b [..., K, N] as l3d_bmm_f32 takes them: 4-d views broadcast over the two batch axes, and the sizes"""
     if a.dtype != torch.float32 or b.dtype != torch.float32 or a.dim() != b.dim() or a.dim() < 2:
         raise ValueError("bmm: fp32 operands with the same number of axes")
     a4, b4 = _as4(a), _as4(b)
@@ -50,7 +50,24 @@ def bmm(a, b, alpha=1.0, out=None, relu=False, bias=None, bias_axis="n", accumul
     K2, N = b4.shape[2:]
     if K != K2:
         raise RuntimeError(f"bmm: inner dimensions {K} and {K2} differ")
-    a4, b4 = a4.expand(nb1, nb2, M, K), b4.expand(nb1, nb2, K, N)
+    return a4.expand(nb1, nb2, M, K), b4.expand(nb1, nb2, K, N), nb1, nb2, M, N, K
+
+
+def bmm_route(a, b, parts=1):
+    """which kernel bmm(a, b, parts=parts) runs (l3d_bmm_f32_route; nothing is launched) -> (YT, A's fetch form, B's fetch form,
+    tiles remapped): YT 2 = 128 x 128 workgroup tiles, 1 = 128 x 64; fetch form 1 / 2 = 16-byte loads along k / along the rows,
+    0 = scalar loads"""
+    a4, b4, nb1, nb2, M, N, K = _bmm_operands(a, b)
+    r = lib().l3d_bmm_f32_route(ptr(a4), _st(a4), ptr(b4), _st(b4), nb1, nb2, M, N, K, int(parts))
+    if r < 0:
+        check(r, "l3d_bmm_f32_route")
+    return (r & L3D_BMM_ROUTE_YT_MASK, (r >> L3D_BMM_ROUTE_A_SHIFT) & 3, (r >> L3D_BMM_ROUTE_B_SHIFT) & 3, bool(r & L3D_BMM_ROUTE_REMAPPED))
+
+
+def bmm(a, b, alpha=1.0, out=None, relu=False, bias=None, bias_axis="n", accumulate=False, parts=1):
+    """a [..., M, K] @ b [..., K, N] (same number of axes, up to two batch axes, any strides -- transposed, sliced or expanded
+    views are read in place) -> act(alpha a b + bias) [..., M, N] fp32.  out: a tensor (any strides) to write / accumulate into."""
+    a4, b4, nb1, nb2, M, N, K = _bmm_operands(a, b)
     given = out is not None
     if out is None:
         out = torch.empty(tuple(torch.broadcast_shapes(a.shape[:-2], b.shape[:-2])) + (M, N), dtype=torch.float32, device=a.device)

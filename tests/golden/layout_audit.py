@@ -32,6 +32,9 @@ STRIDED = {
     ("l3d_bmm_f32", "A"): Strided("a_strides", "strides4", ("nb1", "nb2", "M", "K"), False),
     ("l3d_bmm_f32", "B"): Strided("b_strides", "strides4", ("nb1", "nb2", "K", "N"), False),
     ("l3d_bmm_f32", "C"): Strided("c_strides", "strides4", ("nb1", "nb2", "M", "N"), True),
+    # ... and the host-only query that takes the same operands (it reads the pointers' alignment and the strides, no memory)
+    ("l3d_bmm_f32_route", "A"): Strided("a_strides", "strides4", ("nb1", "nb2", "M", "K"), False),
+    ("l3d_bmm_f32_route", "B"): Strided("b_strides", "strides4", ("nb1", "nb2", "K", "N"), False),
     # l3d_hip.h: `long q_bstride, k_bstride, v_bstride`: "explicit batch strides (in floats) for q, k, v: channel slices of ONE fused
     # projection output [B, 3*H*D, N]"
     ("l3d_attention_forward_strided", "q"): Strided("q_bstride", "batch", ("B", ("H", "D"), "N"), False),

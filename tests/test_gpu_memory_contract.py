@@ -1182,6 +1182,7 @@ def test_entry_point_keeps_its_memory_contract(ident):
 EXEMPT = {
     "l3d_version": "returns a constant", "l3d_status_string": "returns a host string", "l3d_last_hip_error": "reads a host thread-local",
     "l3d_edgeconv_packed_v2_flag_index": "returns a constant",
+    "l3d_bmm_f32_route": "host arithmetic on l3d_bmm_f32's pointers, strides and sizes: which kernel that call would run",
     **{n: "a size function: host arithmetic" for n in (
         "l3d_scatter_add_det_workspace_bytes", "l3d_knn_feature_workspace_bytes", "l3d_chamfer_loss_local_ws_bytes",
         "l3d_chamfer_forward_loss_ws_bytes", "l3d_soft_correspondence_workspace_floats", "l3d_emd_workspace_bytes",

@@ -34,7 +34,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(handle, s), f"{s} declared in include/l3d_hip.h but not exported"
     assert set(syms) == set(_lib.SIGNATURES), "ctypes table and header disagree"
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "l3d_hip.h")).read(), flags=re.S)
-    assert len(set(re.findall(r"\b(l3d_[a-z0-9_]+)\s*\(", text))) <= 97, "the boundary header grew past 97 entry points (90 + l3d_emd_workspace_bytes + l3d_probe_mfma_sustained, round 5; + l3d_chamfer_forward_loss, l3d_colsum_rows and their workspace sizes, l3d_split_f16_operand, round 6)"
+    assert len(set(re.findall(r"\b(l3d_[a-z0-9_]+)\s*\(", text))) <= 98, "the boundary header grew past 98 entry points (90 + l3d_emd_workspace_bytes + l3d_probe_mfma_sustained, round 5; + l3d_chamfer_forward_loss, l3d_colsum_rows and their workspace sizes, l3d_split_f16_operand, round 6; + l3d_bmm_f32_route, the host-only query beside l3d_bmm_f32)"
     l = _lib.lib()
     assert l.l3d_version() >= 100
     assert b"invalid" in l.l3d_status_string(-1)
@@ -50,6 +50,7 @@ def test_prototypes_are_read_from_the_headers():
         "l3d_status_string": (C.c_char_p, [I]),
         "l3d_f16_image_bytes": (SZ, [I, L, I]),
         "l3d_bmm_f32": (I, [P, P, P, P, P, P, I, I, I, I, I, F, I, P, I, P, P]),
+        "l3d_bmm_f32_route": (I, [P, P, P, P, I, I, I, I, I, I]),
         "l3d_bn_finalize": (I, [P, I, I, D, P, P, P, D, I, D, P, P, P, P, P, P, P, P]),
         "l3d_uniform_clouds": (I, [C.c_ulonglong, I, I, F, F, P, P]),
         "l3d_knn_graph": (I, [P, I, I, I, P, P]),
@@ -58,7 +59,7 @@ def test_prototypes_are_read_from_the_headers():
     for name, (restype, argtypes) in want.items():
         assert _lib.PROTOTYPES[name].restype is restype, name
         assert _lib.SIGNATURES[name] == argtypes, name
-    assert len(_lib.SIGNATURES) == 112
+    assert len(_lib.SIGNATURES) == 113
     par = {name: [(p.ctype, p.name) for p in proto.params] for name, proto in _lib.PROTOTYPES.items()}
     assert par["l3d_knn_graph"][4] == ("int64_t *", "idx") and par["l3d_knn_graph"][5] == ("l3d_stream_t", "stream")
     assert par["l3d_bmm_f32"][1] == ("const long *", "a_strides") and par["l3d_bmm_f32"][11] == ("float", "alpha")
@@ -68,6 +69,7 @@ def test_prototypes_are_read_from_the_headers():
     # the integer #defines and the l3d_status enumerators come from the same place
     assert (_lib.L3D_OK, _lib.L3D_ERR_INVALID_ARG, _lib.L3D_ERR_UNSUPPORTED, _lib.L3D_ERR_LAUNCH) == (0, -1, -2, -3)
     assert (_lib.L3D_CONV_F16_TWO_PLANE, _lib.L3D_CONV_F16_OUT_UNSCALED, _lib.L3D_CONV_F16_SHIFT_N, _lib.L3D_KNN_MAX_K) == (1, 2, 4, 200)
+    assert (_lib.L3D_BMM_ROUTE_YT_MASK, _lib.L3D_BMM_ROUTE_A_SHIFT, _lib.L3D_BMM_ROUTE_B_SHIFT, _lib.L3D_BMM_ROUTE_REMAPPED) == (3, 2, 4, 64)
     # the array form of a parameter, and what the parser must refuse
     protos, consts = _lib.parse_header("/* c */\n#define L3D_X 0x10\nint l3d_f(const long st[4], unsigned n,\n          l3d_stream_t stream);\n")
     assert consts == {"L3D_X": 16} and protos["l3d_f"].restype is I
@@ -186,6 +188,24 @@ def test_argument_validation_without_gpu():
     assert l.l3d_furthest_point_sampling(1, 1 << 25, 64, p, p, p, None) == -2                   # tie key: 15 bits of k >> 10
     assert l.l3d_knn_feature(p, 1, 64, 16385, 20, p, p, None) == -2                             # FK_MAXNP = 16384
     assert l.l3d_edge_gather_max(p, p, 1, 64, 32769, 20, 0, p, 64 * 32769, None) == -2          # a channel row of N floats in LDS
+    # l3d_bmm_f32_route: host arithmetic on the pointer's alignment, the strides and the sizes -- l3d_bmm_f32's statuses, else its choice
+    def st(*s):
+        return (C.c_long * 4)(*s)
+    route = lambda a, sa, b, sb, *sizes: l.l3d_bmm_f32_route(a, sa, b, sb, *sizes)
+    al, off = C.c_void_p(p.value & ~15), C.c_void_p((p.value & ~15) + 4)
+    assert route(None, st(0, 0, 8, 1), al, st(0, 0, 8, 1), 1, 1, 8, 8, 8, 1) == -1
+    assert route(al, st(0, 0, 8, 1), al, st(0, 0, 8, 1), 1, 1, 8, 0, 8, 1) == -1
+    assert route(al, st(0, 0, 8, 1), al, st(0, 0, 8, 1), 1, 1, 8, 8, 8, 0) == -1                                   # parts < 1
+    assert route(al, st(0, 0, 8, 1), al, st(0, 0, 8, 1), 256, 256, 8, 8, 8, 1) == -2                               # grid z > 65535
+    assert l.l3d_bmm_f32(al, st(0, 0, 8, 1), al, st(0, 0, 8, 1), al, st(0, 0, 8, 1), 256, 256, 8, 8, 8, 1.0, 0, None, 1, None, None) == -2
+    # A [2048 x 32] plain: 16-byte loads along k (1); B [32 x 1024] plain = rows contiguous (2); 16 x 8 tiles x 4 = 512: YT 2, remapped
+    big = (4, 1, 2048, 1024, 32, 1)
+    assert route(al, st(65536, 0, 32, 1), al, st(32768, 0, 1024, 1), *big) == 2 | 1 << 2 | 2 << 4 | 64
+    assert route(al, st(65536, 0, 1, 2048), al, st(32768, 0, 1, 32), *big) == 2 | 2 << 2 | 1 << 4 | 64               # both transposed
+    assert route(off, st(65536, 0, 32, 1), off, st(32768, 0, 1024, 1), *big) == 2 | 64                             # misaligned: scalar loads
+    assert route(al, st(65536, 0, 32, 1), al, st(32768, 0, 1024, 1), 3, 1, 2048, 1024, 32, 1) == 1 | 1 << 2 | 2 << 4 | 64   # 384 tiles: YT 1
+    assert route(al, st(65536, 0, 32, 1), al, st(32768, 0, 1024, 1), 4, 1, 2100, 1024, 32, 1) == 2 | 1 << 2 | 2 << 4  # 17 row tiles: plain order
+    assert route(al, st(65536, 0, 32, 1), al, st(32768, 0, 64, 1), 64, 1, 2048, 64, 32, 1) == 1 | 1 << 2 | 2 << 4 | 64  # N <= 64 never takes YT 2
 
 
 def test_product_path_fails_loudly_on_cpu_tensors():

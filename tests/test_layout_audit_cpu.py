@@ -35,7 +35,7 @@ def test_every_stride_parameter_of_the_headers_has_a_rule():
     for (name, step), (tensor, full) in layout_audit.DENSE_STEPS.items():
         assert {step, tensor, full} <= {p.name for p in _lib.PROTOTYPES[name].params}, name
     assert sorted({k[0] for k in layout_audit.STRIDED}) == ["l3d_attention_forward_f16b", "l3d_attention_forward_strided", "l3d_bmm_f32",
-                                                            "l3d_colsum_rows", "l3d_edge_gather_max", "l3d_split_f16_operand"]
+                                                            "l3d_bmm_f32_route", "l3d_colsum_rows", "l3d_edge_gather_max", "l3d_split_f16_operand"]
 
 
 def test_a_new_stride_taking_entry_point_fails_the_audit(audited, monkeypatch):

@@ -161,7 +161,7 @@ def test_masknet_header_entries():
     assert all(_lib.PROTOTYPES[n].restype is I for n in want)
     par = [(p.ctype, p.name) for p in _lib.PROTOTYPES["l3d_mask_select"].params]
     assert par[5] == ("float", "threshold") and par[6] == ("int64_t *", "idx") and par[8] == ("int32_t *", "count")
-    assert len(_lib.SIGNATURES) == 112
+    assert len(_lib.SIGNATURES) == 113
     handle = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(handle, "l3d_mask_tail") and hasattr(handle, "l3d_mask_select")
     _lib.lib()                                                           # resolves MaskNet's symbols, too
