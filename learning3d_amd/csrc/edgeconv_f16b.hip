@@ -41,6 +41,20 @@
 //     and no v_fma_mix: v_cvt_pk_f16_f32 (gfx950) rounds the pair to h, two v_cvt_f32_f16 + two v_sub_f32 form the exact
 //     residuals, a second v_cvt_pk_f16_f32 rounds them to m -- six full-rate VALU instructions where the three-plane
 //     kernel issues six v_fma_mix* (measured ~2.4x the issue cost of a plain VALU beside the MFMA stream, LABLOG R2.2).
+//
+// The finish schedule (LABLOG R28.1; tools/ef_gap_model.py prints the model below from the compiled code).  With one wave per SIMD a
+// 16x16x32 MFMA holds the vector issue for 8 of its 16 cycles and every other vector, LDS or VMEM instruction or s_nop costs >= 4:
+// an MFMA gap runs ~ max(16, 8 + 4 c) cycles for c such fillers, two are nearly free, each further one costs its issue.  Layers
+// 2-3 have 60 MFMAs per M-tile pair to hide a ~170-instruction finish behind (every gap overfull), layer 4 has 120 for ~40 (most
+// gaps empty).  So:
+//   * no wait state that an independent instruction can stand in for: the split interleaves two value pairs, the quad reduce of
+//     both M-tiles is two asm blocks with the selects in front of the DPP maxima, a unit is ONE asm block (see "Wait states");
+//   * units are spread over a pair's MFMAs by their instruction count; a layer's first pair runs the deferred pool and
+//     quad-reduce units behind the MFMAs of k-step S-1, which only the plane-making units had to precede;
+//   * PLANES: what happens to a pooled value of layers 1-3 after the quad reduce (range guard, scale, h / m split, staging
+//     stores) is done inside layer 4, two instructions per otherwise empty gap (EfOut, ef_unpark).  PLANES = false keeps its
+//     multiply and 4-byte store where they were: two instructions per value, nothing to stage.
+// The arithmetic, the order of accumulation and every output expression are those of the kernel before: same output bits.
 #include <type_traits>
 #include "common.h"
 #include "edgeconv_layout.h"
@@ -130,46 +144,108 @@ __device__ __forceinline__ float ef_vmax(float a, float b)
     asm volatile("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-__device__ __forceinline__ float ef_vmax3(float a, float b, float c)
+// Wait states.  Nothing pads a hazard inside inline asm, and the compiler's hazard recogniser counts an asm statement as ZERO
+// wait states: wherever one asm statement reads a register that an earlier one wrote, with only asm statements in between (MFMAs
+// included), it places an `s_nop 0` in front of the reader -- a full issue slot beside the MFMA stream.  So each finish unit below
+// is ONE asm block, ordered so that every hazard inside it is covered by independent instructions of the same block:
+//   * VALU write -> DPP read of that VGPR needs 2 wait states: every DPP source is written >= 3 instructions before it is read;
+//   * v_cvt_pk / v_fma_mixlo results are read >= 2 instructions after they are written (two value pairs interleaved).
+// What is left to the compiler is one s_nop where a block reads what another block wrote.
+
+// max over the MT row tiles of one accumulator register
+template <int MT>
+__device__ __forceinline__ float ef_pool_rows(float a0, float a1, float a2, float a3, float a4)
 {
     float r;
-    asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-// d[lane] = max(give[lane ^ 1], keep[lane]) / (lane ^ 2).  The s_nop covers the VALU-write -> DPP-read hazard (2 wait
-// states) that the compiler's hazard recogniser does not see inside inline asm.
-__device__ __forceinline__ float ef_dpp_max_x1(float give, float keep)
-{
-    float r;
-    asm volatile("s_nop 1\n\tv_max_f32_dpp %0, %1, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(give), "v"(keep));
-    return r;
-}
-__device__ __forceinline__ float ef_dpp_max_x2(float give, float keep)
-{
-    float r;
-    asm volatile("s_nop 1\n\tv_max_f32_dpp %0, %1, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(give), "v"(keep));
+    if constexpr (MT == 3) asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a0), "v"(a1), "v"(a2));
+    if constexpr (MT == 4) asm volatile("v_max3_f32 %0, %1, %2, %3\n\tv_max_f32 %0, %0, %4" : "=&v"(r) : "v"(a0), "v"(a1), "v"(a2), "v"(a3));
+    if constexpr (MT == 5)
+        asm volatile("v_max3_f32 %0, %1, %2, %3\n\tv_max3_f32 %0, %0, %4, %5" : "=&v"(r) : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(a4));
     return r;
 }
 
-// relu'd accumulators (scaled domain: a = 2^S y) of one value pair -> packed fp16 (h, m') words of y = a c:
-//   h = f16(a c) (c = 2^-S: the product is exact, one rounding), r = a c - h (exact), m' = f16(r 2^12)
-__device__ __forceinline__ void ef_split_pair(float a0, float a1, float c, uint32_t &h, uint32_t &m)
+// Transposing quad reduce, step 1, of BOTH M-tiles of a pair: per M-tile the four row maxima (a 0..3 / b 0..3) -> two values per
+// lane, x[.][0] = max(give[lane ^ 1], keep) of registers (0, 2), x[.][1] of registers (1, 3); odd = the lanes with q & 1 set.
+// The eight selects stand in front of the four DPP maxima.
+__device__ __forceinline__ void ef_quad_step1(const f32x4 &a, const f32x4 &b, uint64_t odd, f32x2 &xa, f32x2 &xb)
 {
-    // accumulators are already in plane units (c == 1): round the pair, subtract the rounded halves back (exact), round the
-    // residuals.
-    (void)c;
-    asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(a0), "v"(a1));
-    // three instructions per value pair instead of six: v_fma_mixlo/hi_f16 form a * 1.0 - f32(h half) in fp32 (exact: a - h is
-    // representable) and round it to the fp16 half of m in the same instruction -- the same bits as convert, subtract, convert.
-    // s_nop: VALU write -> read of the same VGPR, not seen by the hazard recogniser inside asm.
-    asm volatile("s_nop 0\n\tv_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(m) : "v"(a0), "v"(h));
-    asm volatile("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(m) : "v"(a1), "v"(h));
+    float k0, g0, k1, g1, k2, g2, k3, g3, r0, r1, r2, r3;
+    asm volatile("v_cndmask_b32 %[k0], %[a0], %[a2], %[odd]\n\t"
+                 "v_cndmask_b32 %[g0], %[a2], %[a0], %[odd]\n\t"
+                 "v_cndmask_b32 %[k1], %[a1], %[a3], %[odd]\n\t"
+                 "v_cndmask_b32 %[g1], %[a3], %[a1], %[odd]\n\t"
+                 "v_cndmask_b32 %[k2], %[b0], %[b2], %[odd]\n\t"
+                 "v_cndmask_b32 %[g2], %[b2], %[b0], %[odd]\n\t"
+                 "v_cndmask_b32 %[k3], %[b1], %[b3], %[odd]\n\t"
+                 "v_cndmask_b32 %[g3], %[b3], %[b1], %[odd]\n\t"
+                 "v_max_f32_dpp %[r0], %[g0], %[k0] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "v_max_f32_dpp %[r1], %[g1], %[k1] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "v_max_f32_dpp %[r2], %[g2], %[k2] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "v_max_f32_dpp %[r3], %[g3], %[k3] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+                 : [k0] "=&v"(k0), [g0] "=&v"(g0), [k1] "=&v"(k1), [g1] "=&v"(g1), [k2] "=&v"(k2), [g2] "=&v"(g2), [k3] "=&v"(k3),
+                   [g3] "=&v"(g3), [r0] "=&v"(r0), [r1] "=&v"(r1), [r2] "=&v"(r2), [r3] "=&v"(r3)
+                 : [a0] "v"(a[0]), [a1] "v"(a[1]), [a2] "v"(a[2]), [a3] "v"(a[3]), [b0] "v"(b[0]), [b1] "v"(b[1]), [b2] "v"(b[2]),
+                   [b3] "v"(b[3]), [odd] "s"(odd));
+    xa[0] = r0; xa[1] = r1; xb[0] = r2; xb[1] = r3;
+}
+
+// Step 2 of both M-tiles: v = max(give[lane ^ 2], keep); hi = the lanes with q & 2 set.  Between the two DPP maxima stands the
+// first value's own follow-up (which is what keeps the second one's sources two wait states old):
+//   LAST:      v = max(v, 0)                          (the other layers' values were ReLU'd before pooling)
+//   otherwise: ovf = max(ovf, v * split)              (in plane units: what the next layer's fp16 planes hold)
+template <bool LAST>
+__device__ __forceinline__ void ef_quad_step2(const f32x2 &xa, const f32x2 &xb, uint64_t hi, float split, float &va, float &vb, float &ovf)
+{
+    float k0, g0, k1, g1, t0, t1;
+    if constexpr (LAST) {
+        (void)split; (void)t0; (void)t1; (void)ovf;
+        asm volatile("v_cndmask_b32 %[k0], %[a0], %[a1], %[hi]\n\t"
+                     "v_cndmask_b32 %[g0], %[a1], %[a0], %[hi]\n\t"
+                     "v_cndmask_b32 %[k1], %[b0], %[b1], %[hi]\n\t"
+                     "v_cndmask_b32 %[g1], %[b1], %[b0], %[hi]\n\t"
+                     "v_max_f32_dpp %[va], %[g0], %[k0] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                     "v_max_f32_e64 %[va], %[va], 0\n\t"
+                     "v_max_f32_dpp %[vb], %[g1], %[k1] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                     "v_max_f32_e64 %[vb], %[vb], 0"
+                     : [k0] "=&v"(k0), [g0] "=&v"(g0), [k1] "=&v"(k1), [g1] "=&v"(g1), [va] "=&v"(va), [vb] "=&v"(vb)
+                     : [a0] "v"(xa[0]), [a1] "v"(xa[1]), [b0] "v"(xb[0]), [b1] "v"(xb[1]), [hi] "s"(hi));
+    } else {
+        asm volatile("v_cndmask_b32 %[k0], %[a0], %[a1], %[hi]\n\t"
+                     "v_cndmask_b32 %[g0], %[a1], %[a0], %[hi]\n\t"
+                     "v_cndmask_b32 %[k1], %[b0], %[b1], %[hi]\n\t"
+                     "v_cndmask_b32 %[g1], %[b1], %[b0], %[hi]\n\t"
+                     "v_max_f32_dpp %[va], %[g0], %[k0] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mul_f32 %[t0], %[va], %[sp]\n\t"
+                     "v_max_f32_dpp %[vb], %[g1], %[k1] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mul_f32 %[t1], %[vb], %[sp]\n\t"
+                     "v_max_f32 %[ovf], %[ovf], %[t0]\n\t"
+                     "v_max_f32 %[ovf], %[ovf], %[t1]"
+                     : [k0] "=&v"(k0), [g0] "=&v"(g0), [k1] "=&v"(k1), [g1] "=&v"(g1), [va] "=&v"(va), [vb] "=&v"(vb), [t0] "=&v"(t0),
+                       [t1] "=&v"(t1), [ovf] "+v"(ovf)
+                     : [a0] "v"(xa[0]), [a1] "v"(xa[1]), [b0] "v"(xb[0]), [b1] "v"(xb[1]), [hi] "s"(hi), [sp] "v"(split));
+    }
+}
+
+// relu'd accumulators (already in plane units) of TWO value pairs -> packed fp16 (h, m) words: v_cvt_pk_f16_f32 rounds a pair to
+// h, v_fma_mixlo/hi_f16 form a * 1.0 - f32(h half) in fp32 (exact: a - h is representable) and round it to the fp16 half of m in the
+// same instruction -- the same bits as convert, subtract, convert.  The two pairs alternate, so every result is read two
+// instructions after it is written (one wait state between, as the hand-placed s_nop gave it before).
+__device__ __forceinline__ void ef_split_2pairs(float a0, float a1, float b0, float b1, uint32_t &ha, uint32_t &ma, uint32_t &hb, uint32_t &mb)
+{
+    asm volatile("v_cvt_pk_f16_f32 %0, %4, %5\n\t"
+                 "v_cvt_pk_f16_f32 %2, %6, %7\n\t"
+                 "v_fma_mixlo_f16 %1, %4, 1.0, -%0 op_sel_hi:[0,0,1]\n\t"
+                 "v_fma_mixlo_f16 %3, %6, 1.0, -%2 op_sel_hi:[0,0,1]\n\t"
+                 "v_fma_mixhi_f16 %1, %5, 1.0, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+                 "v_fma_mixhi_f16 %3, %7, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+                 : "=&v"(ha), "=&v"(ma), "=&v"(hb), "=&v"(mb)
+                 : "v"(a0), "v"(a1), "v"(b0), "v"(b1));
 }
 
 // Lane-constant context of the pooled stores.  q = lane & 3 (neighbour slot inside the quad); after the transposing
 // quad reduce lane q holds channel register {0,2,1,3}[q] of its point, and stores it to pooled[point][ch0 + 4g + that].
 struct EfLane {
-    bool odd, hi;            // q & 1, q & 2
+    uint64_t odd, hi;        // the lanes with q & 1 / q & 2 set, as lane masks (a scalar register pair: the selects read them as such)
     unsigned laneoff;        // lane * 16: byte offset of the lane's 16 bytes inside a 1 KB fragment
     ef_rsrc_t rs;            // the packed parameter block
     ef_lds_t w4lds;          // layer 4's fragment block in LDS
@@ -184,6 +260,40 @@ struct EfScale {
     float split, pool;
 };
 
+// What a lane carries out of the finish units.  PLANES: the pooled values of layers 1-3 -- after the quad reduce ONE value per
+// lane and M-tile, 16 per tile -- are PARKED here (AGPRs) by layers 1-3 and go through the rest of their way out (range guard,
+// scale, h / m split, staging stores) in layer 4's empty MFMA gaps (ef_unpark): nothing but the image store waits for them,
+// and in layers 1-3 every issue slot past two per gap costs its full price.
+struct EfOut {
+    float ovf;               // range guard: the largest value (plane units) handed to fp16 planes
+    float park[(EC_C1 + EC_C2 + EC_C3) / 16];
+    float last[2];           // PLANES: the two pooled values of the layer-4 pair whose finish is under way, on the same way out (ef_pair)
+};
+
+// One parked value's way out, as five STAGES of two instructions.  Successive stages of a value are issued a whole execution
+// step (3 MT MFMAs) apart, so the step's fragment reads -- compiler-visible instructions -- stand between the asm statement that
+// writes a register and the one that reads it: no s_nop from the compiler, no hazard.
+struct EfStage {
+    float v, t;              // v = pooled value times sc.pool; t: (float)h, then the residual
+    uint32_t h, m;           // fp16 h and m (low halves)
+};
+// PARKED: the value comes from an AGPR (layers 1-3; staging area A, m plane 2048 bytes behind h) or from a VGPR (layer 4; area
+// B, 256 bytes).
+template <int G, bool PARKED>
+__device__ __forceinline__ void ef_unpark(EfStage &s, float parked, float pool, float mres, float &ovf, ef_ldsw_t cell)
+{
+    typedef __attribute__((address_space(3))) _Float16 *lh_t;
+    if constexpr (G == 0 && PARKED) asm volatile("v_accvgpr_read_b32 %0, %1\n\tv_mul_f32 %0, %2, %0" : "=&v"(s.v) : "a"(parked), "s"(pool));
+    if constexpr (G == 0 && !PARKED) asm volatile("v_mul_f32 %0, %2, %1" : "=v"(s.v) : "v"(parked), "s"(pool));
+    if constexpr (G == 1) asm volatile("v_max_f32 %0, %0, %2\n\tv_cvt_f16_f32 %1, %2" : "+v"(ovf), "=&v"(s.h) : "v"(s.v));
+    if constexpr (G == 2) asm volatile("v_cvt_f32_f16 %0, %1\n\tv_sub_f32 %0, %2, %0" : "=&v"(s.t) : "v"(s.h), "v"(s.v));
+    if constexpr (G == 3) asm volatile("v_mul_f32 %0, %2, %1\n\tv_cvt_f16_f32 %0, %0" : "=&v"(s.m) : "v"(s.t), "s"(mres));
+    if constexpr (G == 4) {
+        *(lh_t)cell = __builtin_bit_cast(_Float16, (uint16_t)s.h);
+        *(lh_t)(cell + (PARKED ? 2048 : 256)) = __builtin_bit_cast(_Float16, (uint16_t)s.m);
+    }
+}
+
 // Scratch values that live from one micro-unit to the next
 struct EfTmp {
     f32x4 mx[2];             // max over the row tiles, per M-tile
@@ -192,37 +302,57 @@ struct EfTmp {
 };
 
 // ---------------------------------------------------------------------------------------------
-// The finish work of a completed M-tile pair (ReLU, two-plane split, max-pool) as MICRO-UNITS of 2-8 VALU instructions,
-// issued one by one between the MFMAs of the next pair (with one wave per SIMD nothing else hides VALU work):
-//   not LAST:  per row tile t: [relu h0[t]] [relu h1[t]] [split pair 0] [1] [2] [3 + the two fragments -> AGPRs]
-//              then 8 x [pool one register of one M-tile], 2 x ([quad reduce, step 1] [step 2 + store])  = 6 MT + 12
-//   LAST:      the 8 pool and 4 quad units on the raw accumulators, ReLU on the one pooled value per lane      = 12
+// The finish work of a completed M-tile pair (ReLU, two-plane split, max-pool) as MICRO-UNITS of 2-12 VALU instructions,
+// issued between the MFMAs of the next pair (with one wave per SIMD nothing else hides VALU work):
+//   not LAST:  per row tile t: 2 x [relu half of h0[t]] 2 x [of h1[t]] [split value pairs 0, 1] [pairs 2, 3 + the two fragments -> AGPRs]
+//              then 8 x [pool one register of one M-tile], [quad reduce step 1, both M-tiles] [step 2 + store]   = 6 MT + 10
+//   LAST:      the 8 pool and 2 quad units on the raw accumulators, ReLU on the one pooled value per lane        = 10
 // ORDER is the MFMA -> VALU hazard cover: the first units touch M-tile 0 only (finished a whole step earlier);
-// h1[MT-1], written by the pair's very last MFMA, is first read by unit 6 (MT-1) + 1 resp. pool unit 4.
+// h1[t], written by the pair's MFMA MT - t from its end, is first read by unit 6 t + 2 resp. pool unit 4 -- at least five MFMAs
+// later wherever the units are spread over the next pair's MFMAs by EfN::first (unit 6 t + 2 never rides before slot t + 1).
 // The quad reduce is a transposing butterfly: 4 registers x 4 lanes -> ONE value per lane in 3 DPP max (+6 selects),
 // and every lane stores its dword -- no `if (writer)` exec-mask branch.
-// RAW = false (layer 1's accumulators come from MFMA builtins, straight after them): the first reader of every
-// accumulator is a compiler-visible instruction, so the compiler pads the hazard.
+// RAW = false: the accumulators come from MFMA builtins and the first reader of each is a compiler-visible instruction, so
+// the compiler pads the hazard (no caller at present: layer 1 issues its MFMAs as asm too).
 // ---------------------------------------------------------------------------------------------
-template <int MT, bool LAST> struct EfN { static constexpr int UNITS = LAST ? 12 : 6 * MT + 12; };
+template <int MT, bool LAST> struct EfN {
+    static constexpr int NT = LAST ? 0 : 6 * MT;             // units before the pool units
+    static constexpr int UNITS = NT + 10;
+    // issue slots of a unit, roughly (a split unit's AGPR homes and the output path behind the quad reduce are the compiler's to
+    // place: counted with their unit)
+    static constexpr int weight(int u) { return u < NT ? (u % 6 < 4 ? 2 : 8) : u < NT + 8 ? 2 : u == NT + 8 ? 12 : LAST ? 20 : 12; }
+    // Units [u0, u1) spread over n MFMA slots BY WEIGHT (unit u rides behind slot cum(u) n / W, cum = the weights in front of it):
+    // the first unit that rides at or behind slot s; slot s takes [first(s), first(s + 1)).
+    static constexpr int first(int u0, int u1, int n, int s)
+    {
+        int W = 0, cum = 0;
+        for (int u = u0; u < u1; u++) W += weight(u);
+        for (int u = u0; u < u1; u++) {
+            if (cum * n / W >= s) return u;
+            cum += weight(u);
+        }
+        return u1;
+    }
+};
 
 template <int MT, bool LAST, bool RAW, bool PLANES, int U>
-__device__ __forceinline__ void ef_micro(f32x4 (&h)[2][MT], f16x8 (&pl)[2][MT], EfTmp &T, int ch0, const EfLane &L, const EfScale &sc, float &ovf)
+__device__ __forceinline__ void ef_micro(f32x4 (&h)[2][MT], f16x8 (&pl)[2][MT], EfTmp &T, int ch0, const EfLane &L, const EfScale &sc, EfOut &O)
 {
-    const float c = sc.split;
-    constexpr int NT = LAST ? 0 : 6 * MT;                    // units before the pool units
+    constexpr int NT = EfN<MT, LAST>::NT;
     if constexpr (U < NT) {
         constexpr int t = U / 6, k = U % 6;
-        if constexpr (k < 2) {                               // relu of M-tile k, row tile t
+        if constexpr (k < 4) {                               // relu of M-tile k / 2, row tile t, two registers
 #pragma unroll
-            for (int r = 0; r < 4; r++) h[k][t][r] = RAW ? ef_vmax(h[k][t][r], 0.f) : fmaxf(h[k][t][r], 0.f);
-        } else {                                             // split value pair k-2 of the (M-tile pair, row tile t) fragment
-            constexpr int i = k - 2;
-            uint32_t a, b;
-            ef_split_pair(h[i >> 1][t][2 * (i & 1)], h[i >> 1][t][2 * (i & 1) + 1], c, a, b);
-            T.qh[i] = a;
-            T.qm[i] = b;
-            if constexpr (i == 3) {                          // whole 16-byte fragments, homed in AGPRs: the type the MFMA reads
+            for (int r = 2 * (k & 1); r < 2 * (k & 1) + 2; r++) h[k >> 1][t][r] = RAW ? ef_vmax(h[k >> 1][t][r], 0.f) : fmaxf(h[k >> 1][t][r], 0.f);
+        } else {                                             // split the four values of M-tile k-4, row tile t: words 2 (k-4), 2 (k-4) + 1 of the fragment
+            constexpr int m = k - 4;
+            uint32_t ha, ma, hb, mb;
+            ef_split_2pairs(h[m][t][0], h[m][t][1], h[m][t][2], h[m][t][3], ha, ma, hb, mb);
+            T.qh[2 * m] = ha;
+            T.qm[2 * m] = ma;
+            T.qh[2 * m + 1] = hb;
+            T.qm[2 * m + 1] = mb;
+            if constexpr (m == 1) {                          // whole 16-byte fragments, homed in AGPRs: the type the MFMA reads
                 pl[0][t] = ef_home_agpr(T.qh);
                 pl[1][t] = ef_home_agpr(T.qm);
             }
@@ -231,46 +361,28 @@ __device__ __forceinline__ void ef_micro(f32x4 (&h)[2][MT], f16x8 (&pl)[2][MT], 
         constexpr int k = (U - NT) / 4, r = (U - NT) % 4;
         static_assert(MT >= 3 && MT <= 5, "row tiles per wave");
         if constexpr (RAW) {
-            float m = ef_vmax3(h[k][0][r], h[k][1][r], h[k][2][r]);
-            if constexpr (MT == 4) m = ef_vmax(m, h[k][3][r]);
-            if constexpr (MT == 5) m = ef_vmax3(m, h[k][3][r], h[k][4][r]);
-            T.mx[k][r] = m;
+            T.mx[k][r] = ef_pool_rows<MT>(h[k][0][r], h[k][1][r], h[k][2][r], h[k][MT > 3 ? 3 : 0][r], h[k][MT > 4 ? 4 : 0][r]);
         } else {
             float m = h[k][0][r];
 #pragma unroll
             for (int t = 1; t < MT; t++) m = fmaxf(m, h[k][t][r]);
             T.mx[k][r] = m;
         }
-    } else {                                                 // transposing quad reduce, ReLU (LAST), scale, store
-        constexpr int k = (U - NT - 8) / 2, part = (U - NT - 8) % 2;
-        if constexpr (part == 0) {
-            const float k0 = L.odd ? T.mx[k][2] : T.mx[k][0], g0 = L.odd ? T.mx[k][0] : T.mx[k][2];
-            const float k1 = L.odd ? T.mx[k][3] : T.mx[k][1], g1 = L.odd ? T.mx[k][1] : T.mx[k][3];
-            T.xs[k][0] = ef_dpp_max_x1(g0, k0);
-            T.xs[k][1] = ef_dpp_max_x1(g1, k1);
-        } else {
-            const float kk = L.hi ? T.xs[k][1] : T.xs[k][0], gg = L.hi ? T.xs[k][0] : T.xs[k][1];
-            float v = ef_dpp_max_x2(gg, kk);
-            if constexpr (LAST) v = ef_vmax(v, 0.f);         // non-LAST values were ReLU'd before pooling
-            if constexpr (!LAST) ovf = ef_vmax(ovf, v * sc.split);   // in plane units: what the next layer's fp16 planes hold
-            v *= sc.pool;
-            if constexpr (PLANES) {                          // pooled output as fp16 planes (times 2^T_out) for conv_f16.hip
-                ovf = ef_vmax(ovf, v);
-                const _Float16 hh = (_Float16)v;
-                const _Float16 mm = (_Float16)((v - (float)hh) * L.mres);
-                typedef __attribute__((address_space(3))) _Float16 *lh_t;
-                if constexpr (!LAST) {                       // layers 1-3: area A, cell row (ch0 + 16 k) / 8 (+ 1 inside the lane part)
-                    const int off = ((ch0 + 16 * k) >> 3) * 64;
-                    *(lh_t)(L.stgA + off) = hh;
-                    *(lh_t)(L.stgA + off + 2048) = mm;
-                } else {                                     // layer 4, pair m: area B, chunk (m >> 1) & 1, slot m & 1, cell rows 2 k (+ 1)
-                    const int m = (ch0 - (EC_C1 + EC_C2 + EC_C3)) >> 5;
-                    const int off = ((m >> 1) & 1) * 1024 + (m & 1) * 512 + (2 * k) * 64;
-                    *(lh_t)(L.stgB + off) = hh;
-                    *(lh_t)(L.stgB + off + 256) = mm;
-                }
+    } else if constexpr (U == NT + 8) {                      // transposing quad reduce of both M-tiles, step 1
+        ef_quad_step1(T.mx[0], T.mx[1], L.odd, T.xs[0], T.xs[1]);
+    } else {                                                 // step 2, ReLU (LAST), range guard, scale, store
+        float vk[2];
+        ef_quad_step2<LAST>(T.xs[0], T.xs[1], L.hi, sc.split, vk[0], vk[1], O.ovf);
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            if constexpr (PLANES && !LAST) {                 // layers 1-3: parked; the way out is ef_unpark's, inside layer 4
+                float p = vk[k];                             // (ch0 is a literal at every call site: the index folds to a constant)
+                asm("" : "+a"(p));
+                O.park[(ch0 >> 4) + k] = p;
+            } else if constexpr (PLANES) {                   // layer 4: the way out is ef_last_stage's, behind later MFMAs of the same pair
+                O.last[k] = vk[k];
             } else {
-                L.prow[ch0 + 16 * k] = v;
+                L.prow[ch0 + 16 * k] = vk[k] * sc.pool;
             }
         }
     }
@@ -288,11 +400,27 @@ __device__ __forceinline__ void ef_static_for(F &&f)
     }
 }
 
+// Stage G of the way out of O.last[k], the pooled value of M-tile k of the layer-4 pair at channel ch0 (pair m: area B, chunk
+// (m >> 1) & 1, slot m & 1, cell rows 2 k (+ 1)).
+template <int G>
+__device__ __forceinline__ void ef_last_stage(EfStage &s, EfOut &O, int k, int ch0, const EfLane &L, const EfScale &sc)
+{
+    const int m = (ch0 - (EC_C1 + EC_C2 + EC_C3)) >> 5;
+    ef_unpark<G, false>(s, O.last[k], sc.pool, L.mres, O.ovf, L.stgB + ((m >> 1) & 1) * 1024 + (m & 1) * 512 + (2 * k) * 64);
+}
+
 template <int MT, bool LAST, bool RAW, bool PLANES>
-__device__ __forceinline__ void ef_finish_all(f32x4 (&h)[2][MT], f16x8 (&pl)[2][MT], int ch0, const EfLane &L, const EfScale &sc, float &ovf)
+__device__ __forceinline__ void ef_finish_all(f32x4 (&h)[2][MT], f16x8 (&pl)[2][MT], int ch0, const EfLane &L, const EfScale &sc, EfOut &O)
 {
     EfTmp T;
-    ef_static_for<0, EfN<MT, LAST>::UNITS>([&](auto u) { ef_micro<MT, LAST, RAW, PLANES, decltype(u)::value>(h, pl, T, ch0, L, sc, ovf); });
+    ef_static_for<0, EfN<MT, LAST>::UNITS>([&](auto u) { ef_micro<MT, LAST, RAW, PLANES, decltype(u)::value>(h, pl, T, ch0, L, sc, O); });
+    if constexpr (LAST && PLANES) {
+        EfStage s[2];
+        ef_static_for<0, 5>([&](auto g) {
+            ef_last_stage<decltype(g)::value>(s[0], O, 0, ch0, L, sc);
+            ef_last_stage<decltype(g)::value>(s[1], O, 1, ch0, L, sc);
+        });
+    }
 }
 
 // EF_PIN: the compiler's IR passes sink a load towards its first use (two steps later) regardless of
@@ -343,22 +471,37 @@ __device__ __forceinline__ void ef_ring_fill(EfRing &R, ef_rsrc_t rs, int woff, 
 }
 
 // One output M-tile pair of a dense layer: 2 x S steps (k-step outer, M-tile inner -- the order the
-// fragments are packed in) of {prefetch fragment step+EF_PD, 3 products x MT MFMAs}, with one micro-unit of the finish
-// of a PREVIOUS pair (hp) after each of the first NSL MFMAs.  That previous pair is the preceding pair of this layer
-// (NSL = every MFMA slot) or, for a layer's first pair, the LAST pair of the previous layer, whose planes are this
-// layer's k-step S-1: its units then ride on the MFMAs of k-steps 0 .. S-2 only and are complete (plus an s_nop for
-// the accvgpr-write -> MFMA-read hazard) before the first MFMA that reads them.
+// fragments are packed in) of {prefetch fragment step+EF_PD, 3 products x MT MFMAs}, with the micro-units of the finish
+// of a PREVIOUS pair (hp) spread BY THEIR WEIGHT (EfN::first) behind the MFMAs.  That previous pair is the preceding pair of
+// this layer (NSL = every MFMA slot) or, for a layer's first pair, the LAST pair of the previous layer, whose planes are this
+// layer's k-step S-1: the units that make those planes (ReLU, split, AGPR homes) then ride on the MFMAs of k-steps 0 .. S-2
+// only and are complete (plus an s_nop for the accvgpr-write -> MFMA-read hazard) before the first MFMA that reads them,
+// and its pool and quad-reduce units, which no MFMA waits for, ride on the MFMAs of k-step S-1.
 // mp = this pair; nx = the pair executed after it, in this layer or the first of the next (fragment and bias
 // prefetches cross both boundaries); pairs may be executed in any order.  R.bv: this pair's bias (the MFMA C operand of
 // each M-tile's first product); replaced by the next pair's on return.  c_prev: 2^-S of hp's layer.
-template <int MT, int S, bool PREV_LAST, bool PREV_RAW, bool PLANES, int NSL, bool OWN_LDS = false, bool NX_LDS = false>
+struct EfNoHook { template <class... I> __device__ __forceinline__ void operator()(I...) const {} };
+
+// extra(slot): further work that rides behind MFMA slot `slot` of this pair (layer 4: the parked values' way out).
+template <int MT, int S, bool PREV_LAST, bool PREV_RAW, bool PLANES, int NSL, bool OWN_LDS = false, bool NX_LDS = false, class EXTRA = EfNoHook>
 __device__ __forceinline__ void ef_pair(int mp, const EfNext &nx, const f16x8 (&pin)[S][2][MT], const f16x8 (&pin_last)[2][MT],
                                         int woff, EfRing &R,
                                         f32x4 (&acc)[2][MT], f32x4 (&hp)[2][MT], f16x8 (&po_prev)[2][MT],
-                                        int ch_prev, const EfLane &L, const EfScale &c_prev, float &ovf)
+                                        int ch_prev, const EfLane &L, const EfScale &c_prev, EfOut &O, EXTRA &&extra = EfNoHook())
 {
     static_assert(2 * S >= EF_PD, "a pair is at least EF_PD steps long");
-    constexpr int NU = EfN<MT, PREV_LAST>::UNITS;                    // micro-units to hide
+    typedef EfN<MT, PREV_LAST> E;
+    constexpr int NU = E::UNITS, NS = 2 * S * 3 * MT;                // micro-units to hide; MFMA slots of the pair
+    // deferred finish (NSL < NS): only the units that make the planes must be complete before k-step S-1; the pool and quad units,
+    // which no MFMA waits for, ride on the MFMAs of k-step S-1
+    constexpr int NA = NSL < NS ? E::NT : NU;
+    // the finish of a layer-4 pair with PLANES: its units ride on the first steps, the two pooled values then take their way out
+    // one stage per step over the last five (behind slots 5 and 10 of the step)
+    constexpr bool WAYOUT = PREV_LAST && PLANES;
+    constexpr int NSU = WAYOUT ? (2 * S - 5) * 3 * MT : NSL;          // slots that carry units
+    static_assert(!WAYOUT || (2 * S > 5 && NSL == NS), "five steps for the way out");
+    EfStage TS[2];
+    static_assert(NSL == NS || !PREV_LAST, "a deferred finish is the finish of a layer that has planes");
     EfTmp T;
     ef_static_for<0, 2 * S>([&](auto rc) {
         // execution step r = 2 s + mm; fragment EF_PD steps ahead: inside this pair, or the first steps of the next
@@ -389,10 +532,14 @@ __device__ __forceinline__ void ef_pair(int mp, const EfNext &nx, const f16x8 (&
                 if constexpr (s == 0 && prod == 0) ef_mfma_init(acc[mm][t], R.a[0][pa], bop, R.bv[mm]);
                 else ef_mfma_acc(acc[mm][t], R.a[0][pa], bop);
                 constexpr int slot = (r * 3 + prod) * MT + t;
-                if constexpr (slot < NSL)
-                    ef_static_for<slot * NU / NSL, (slot + 1) * NU / NSL>([&](auto u) {
-                        ef_micro<MT, PREV_LAST, PREV_RAW, PLANES, decltype(u)::value>(hp, po_prev, T, ch_prev, L, c_prev, ovf);
-                    });
+                constexpr int ub = slot < NSU ? E::first(0, NA, NSU, slot) : WAYOUT ? NU : E::first(NA, NU, NS - NSL, slot - NSL);
+                constexpr int ue = slot < NSU ? E::first(0, NA, NSU, slot + 1) : WAYOUT ? NU : E::first(NA, NU, NS - NSL, slot + 1 - NSL);
+                ef_static_for<ub, ue>([&](auto u) {
+                    ef_micro<MT, PREV_LAST, PREV_RAW, PLANES, decltype(u)::value>(hp, po_prev, T, ch_prev, L, c_prev, O);
+                });
+                if constexpr (WAYOUT && slot >= NSU && (slot % (3 * MT) == 5 || slot % (3 * MT) == 10))
+                    ef_last_stage<(slot - NSU) / (3 * MT)>(TS[slot % (3 * MT) == 10], O, slot % (3 * MT) == 10, ch_prev, L, c_prev);
+                extra(std::integral_constant<int, slot>{});
             });
         });
         if constexpr (r == 1) {                                       // both M-tiles have consumed their bias: fetch the next pair's
@@ -418,14 +565,14 @@ __device__ __forceinline__ void ef_pair(int mp, const EfNext &nx, const f16x8 (&
 // array is indexed by the pair): this workgroup starts at pair `rot`.
 // IN_RAW: accB on entry was produced by asm MFMAs (layers >= 2) rather than builtins (layer 1).
 // c_in / c_own: 2^-S of the previous layer (whose last pair is finished here) and of this layer; bias is pre-scaled.
-struct EfNoHook { template <class I> __device__ __forceinline__ void operator()(I) const {} };
 
-template <int MT, int S, int NPAIR, bool LAST, bool UNROLL, bool IN_RAW, bool PLANES, class HOOK = EfNoHook, bool OWN_LDS = false, bool AFTER_LDS = false>
+template <int MT, int S, int NPAIR, bool LAST, bool UNROLL, bool IN_RAW, bool PLANES, class HOOK = EfNoHook, bool OWN_LDS = false, bool AFTER_LDS = false,
+          class EXTRA = EfNoHook>
 __device__ __forceinline__ void ef_layer(const f16x8 (&pin)[S][2][MT], f16x8 (&pout)[LAST ? 1 : NPAIR][2][MT],
                                          int woff, ef_ldsf_t bias4g, const EfNext &after, EfRing &R, int ch_own,
                                          f32x4 (&accA)[2][MT], f32x4 (&accB)[2][MT], int ch_in,
-                                         int *mp_out, const EfLane &L, int rot, const EfScale &c_in, const EfScale &c_own, float &ovf,
-                                         HOOK &&hook = EfNoHook())
+                                         int *mp_out, const EfLane &L, int rot, const EfScale &c_in, const EfScale &c_own, EfOut &O,
+                                         HOOK &&hook = EfNoHook(), EXTRA &&extra = EfNoHook())
 {
     static_assert(NPAIR % 2 == 0 && S >= 2, "pairs are processed two at a time; deferred finish needs S >= 2");
     constexpr int NS = 2 * S * 3 * MT, NSD = (S - 1) * 6 * MT;      // MFMA slots of a pair; of its k-steps 0 .. S-2
@@ -436,14 +583,14 @@ __device__ __forceinline__ void ef_layer(const f16x8 (&pin)[S][2][MT], f16x8 (&p
         // unrolled, and a rolled loop indexes pout dynamically, which sends the planes to scratch
         static_assert(NPAIR == 2 || NPAIR == 4, "unrolled layers have 2 or 4 output pairs");
         static_assert(!OWN_LDS, "only the rolled (last) layer keeps its weights in LDS");
-        ef_pair<MT, S, false, IN_RAW, PLANES, NSD>(0, in_layer(1), pin, last, woff, R, accA, accB, last, ch_in, L, c_in, ovf);
+        ef_pair<MT, S, false, IN_RAW, PLANES, NSD>(0, in_layer(1), pin, last, woff, R, accA, accB, last, ch_in, L, c_in, O);
         if constexpr (NPAIR > 2)
-            ef_pair<MT, S, LAST, true, PLANES, NS>(1, in_layer(2), pin, last, woff, R, accB, accA, pout[0], ch_own, L, c_own, ovf);
+            ef_pair<MT, S, LAST, true, PLANES, NS>(1, in_layer(2), pin, last, woff, R, accB, accA, pout[0], ch_own, L, c_own, O);
         else
-            ef_pair<MT, S, LAST, true, PLANES, NS, false, AFTER_LDS>(1, after, pin, last, woff, R, accB, accA, pout[0], ch_own, L, c_own, ovf);
+            ef_pair<MT, S, LAST, true, PLANES, NS, false, AFTER_LDS>(1, after, pin, last, woff, R, accB, accA, pout[0], ch_own, L, c_own, O);
         if constexpr (NPAIR == 4) {
-            ef_pair<MT, S, LAST, true, PLANES, NS>(2, in_layer(3), pin, last, woff, R, accA, accB, pout[1], ch_own + 32, L, c_own, ovf);
-            ef_pair<MT, S, LAST, true, PLANES, NS, false, AFTER_LDS>(3, after, pin, last, woff, R, accB, accA, pout[2], ch_own + 64, L, c_own, ovf);
+            ef_pair<MT, S, LAST, true, PLANES, NS>(2, in_layer(3), pin, last, woff, R, accA, accB, pout[1], ch_own + 32, L, c_own, O);
+            ef_pair<MT, S, LAST, true, PLANES, NS, false, AFTER_LDS>(3, after, pin, last, woff, R, accB, accA, pout[2], ch_own + 64, L, c_own, O);
         }
         *mp_out = NPAIR - 1;
     } else {
@@ -451,18 +598,19 @@ __device__ __forceinline__ void ef_layer(const f16x8 (&pin)[S][2][MT], f16x8 (&p
         // but a rolled loop whose body differs per trip (hook) made the compiler merge its memory counters at every join:
         // `s_waitcnt vmcnt(0)` inside the MFMA stream, behind all stores in flight).  hook(i) runs in front of pair i.
         (void)rot;
-        ef_pair<MT, S, false, IN_RAW, PLANES, NSD, OWN_LDS, OWN_LDS>(0, in_layer(1), pin, last, woff, R, accA, accB, last, ch_in, L, c_in, ovf);
+        ef_pair<MT, S, false, IN_RAW, PLANES, NSD, OWN_LDS, OWN_LDS>(0, in_layer(1), pin, last, woff, R, accA, accB, last, ch_in, L, c_in, O);
         ef_static_for<1, NPAIR>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             hook(ic);
             constexpr bool more = i + 1 < NPAIR;
             const EfNext nx = more ? in_layer(i + 1) : after;
+            auto ex = [&](auto sc) { extra(ic, sc); };                // extra(pair, slot)
             if constexpr (i & 1)
-                ef_pair<MT, S, LAST, true, PLANES, NS, OWN_LDS, more ? OWN_LDS : AFTER_LDS>(i, nx, pin, last, woff, R, accB, accA, pout[0],
-                                                                                          ch_own + 32 * (i - 1), L, c_own, ovf);
+                ef_pair<MT, S, LAST, true, PLANES, NS, OWN_LDS, more ? OWN_LDS : AFTER_LDS, decltype(ex) &>(i, nx, pin, last, woff, R, accB, accA, pout[0],
+                                                                                                           ch_own + 32 * (i - 1), L, c_own, O, ex);
             else
-                ef_pair<MT, S, LAST, true, PLANES, NS, OWN_LDS, more ? OWN_LDS : AFTER_LDS>(i, nx, pin, last, woff, R, accA, accB, pout[0],
-                                                                                          ch_own + 32 * (i - 1), L, c_own, ovf);
+                ef_pair<MT, S, LAST, true, PLANES, NS, OWN_LDS, more ? OWN_LDS : AFTER_LDS, decltype(ex) &>(i, nx, pin, last, woff, R, accA, accB, pout[0],
+                                                                                                           ch_own + 32 * (i - 1), L, c_own, O, ex);
         });
         *mp_out = NPAIR - 1;
     }
@@ -541,8 +689,8 @@ __global__ __launch_bounds__(256, 1) void EF_KERNEL(const float *__restrict__ xy
     EfLane L;
     L.laneoff = (unsigned)lane * 16u;
     L.rs.p = (const char *)packed;
-    L.odd = j & 1;
-    L.hi = j & 2;
+    L.odd = __ballot(j & 1);
+    L.hi = __ballot(j & 2);
     const int cl = 4 * g + ((j & 1) * 2 + ((j >> 1) & 1));       // this lane's channel inside a 16-channel M-tile
     L.bn = (size_t)B * N;
     L.mres = mres;
@@ -563,7 +711,8 @@ __global__ __launch_bounds__(256, 1) void EF_KERNEL(const float *__restrict__ xy
     const int po = PLANES ? 8 : 4;
     const EfScale s1 = {packed[EFO_SC + 0], packed[EFO_SC + po + 0]}, s2 = {packed[EFO_SC + 1], packed[EFO_SC + po + 1]},
                   s3 = {packed[EFO_SC + 2], packed[EFO_SC + po + 2]}, s4 = {1.0f, packed[EFO_SC + po + 3]};
-    float ovf = 0.f;
+    EfOut O;
+    O.ovf = 0.f;
     constexpr int w2 = EFO_W2 * 4, w3 = EFO_W3 * 4, w4 = EFO_W4 * 4;      // byte offsets inside the descriptor
     const ef_ldsf_t bs2 = (ef_ldsf_t)((ef_lds_t)ef_lds + EF_LOFF_B2) + 4 * g, bs3 = (ef_ldsf_t)((ef_lds_t)ef_lds + EF_LOFF_B3) + 4 * g,
                     bs4 = (ef_ldsf_t)((ef_lds_t)ef_lds + EF_LOFF_B4) + 4 * g;
@@ -636,7 +785,7 @@ __global__ __launch_bounds__(256, 1) void EF_KERNEL(const float *__restrict__ xy
         f32x4 bv1[EC_C1 / 16];
 #pragma unroll
         for (int m = 0; m < EC_C1 / 16; m++) { a1[m] = w1[m * 64 + lane]; bv1[m] = *(lb1_t)(b1p + 16 * m); }
-        // pair 0 -> accA, pair 1 -> accB; pair 0's finish (ReLU, split into p1[0], pooling: 6 MT + 12 micro-units) rides on pair 1's
+        // pair 0 -> accA, pair 1 -> accB; pair 0's finish (ReLU, split into p1[0], pooling: 6 MT + 10 micro-units) rides on pair 1's
         // MFMAs -- a v_mfma_f32_16x16x4_f32 holds the matrix pipe for 32 cycles -- instead of standing between the two pairs
         static_assert(EC_C1 == 64, "layer 1 is two M-tile pairs");
         auto mfma1 = [&](f32x4 &d, float a, float b, const f32x4 &c, bool first) {
@@ -660,8 +809,8 @@ __global__ __launch_bounds__(256, 1) void EF_KERNEL(const float *__restrict__ xy
         ef_static_for<0, NSL1>([&](auto sc) {
             constexpr int slot = decltype(sc)::value, mm = slot / (2 * MT), s = (slot / MT) % 2, t = slot % MT;
             mfma1(accB[mm][t], a1[2 + mm][s], b1[t][s], bv1[2 + mm], s == 0);
-            ef_static_for<slot * NU1 / NSL1, (slot + 1) * NU1 / NSL1>([&](auto u) {
-                ef_micro<MT, false, true, PLANES, decltype(u)::value>(accA, p1[0], T1, 0, L, s1, ovf);
+            ef_static_for<EfN<MT, false>::first(0, NU1, NSL1, slot), EfN<MT, false>::first(0, NU1, NSL1, slot + 1)>([&](auto u) {
+                ef_micro<MT, false, true, PLANES, decltype(u)::value>(accA, p1[0], T1, 0, L, s1, O);
             });
         });
         // An MFMA reads its C operand over its passes, and nothing pads an asm MFMA: the bias registers must not be handed out as
@@ -677,23 +826,23 @@ __global__ __launch_bounds__(256, 1) void EF_KERNEL(const float *__restrict__ xy
     f16x8 p2[EC_C2 / 32][2][MT];
     ef_layer<MT, EC_C1 / 32, EC_C2 / 32, false, true, true, PLANES>(
         p1, p2, w2, bs2, EfNext{w3, bs3, 0, 2 * (EC_C2 / 32)}, R, EC_C1, accA, accB,
-        32 * (EC_C1 / 32 - 1), &mp_last, L, 0, s1, s2, ovf);
+        32 * (EC_C1 / 32 - 1), &mp_last, L, 0, s1, s2, O);
     EF_T(3);
     // ---- layer 3: 64 -> 128; its last pair prefetches layer 4's first fragments from LDS
     f16x8 p3[EC_C3 / 32][2][MT];
     ef_layer<MT, EC_C2 / 32, EC_C3 / 32, false, true, true, PLANES, EfNoHook, false, true>(
         p2, p3, w3, bs3, EfNext{w4, bs4, 0, 2 * (EC_C3 / 32)}, R, EC_C1 + EC_C2, accA, accB,
-        EC_C1 + 32 * (EC_C2 / 32 - 1), &mp_last, L, 0, s2, s3, ovf);
+        EC_C1 + 32 * (EC_C2 / 32 - 1), &mp_last, L, 0, s2, s3, O);
     EF_T(4);
     // ---- layer 4: 128 -> 256, only max-pooled; its last pair prefetches layer 2's first fragments for the next tile.
     // In front of its pairs (hook): the staged pooled planes of this tile leave as 16-byte stores -- one ds_read_b128 per trip,
-    // stored one pair later (area A: layers 1-3, complete once pair 0 has finished layer 3's last pair; area B: two layer-4
-    // pairs per 1 KB chunk, chunk (m >> 1) & 1) -- and the next tile's gather goes out (indices before pair 2, the coordinates they
+    // stored one pair later (area A: layers 1-3, staged by the parked values' way out behind pairs 1 and 2, read in front of
+    // pairs 3 .. 6; area B: two layer-4 pairs per 1 KB chunk, chunk (m >> 1) & 1) -- and the next tile's gather goes out (indices before pair 2, the coordinates they
     // point to before pair 6), waited for before pair 7, where every count is known, instead of behind the loop's back edge.
     f16x8 dummy[1][2][MT];
-    u32x4 X;                                                     // the 16 bytes on their way from LDS to the image
+    u32x4 X, XA;                                                 // 16 bytes on their way from LDS to the image: of area B, of area A
 #define EF_ST16(ptr, val) (*(u32x4 *)(ptr) = (val))
-    auto st_a = [&](int c) { EF_ST16(img_pt + (size_t)((c >> 1) * 64 + (c & 1) * 16 + (lane >> 2)) * row_bytes, X); EF_PIN(); };
+    auto st_a = [&](int c) { EF_ST16(img_pt + (size_t)((c >> 1) * 64 + (c & 1) * 16 + (lane >> 2)) * row_bytes, XA); EF_PIN(); };
     auto st_b = [&](int m0) {                                    // chunk of pairs m0, m0 + 1: lane -> slot, plane, cell row, point
         const int row = ((lane >> 4) & 1) * 64 + (EC_C1 + EC_C2 + EC_C3) / 8 + 4 * (m0 + (lane >> 5)) + ((lane >> 2) & 3);
         EF_ST16(img_pt + (size_t)row * row_bytes, X);
@@ -702,10 +851,10 @@ __global__ __launch_bounds__(256, 1) void EF_KERNEL(const float *__restrict__ xy
     auto hook = [&](auto ic) {
         constexpr int i = decltype(ic)::value;
         if constexpr (PLANES) {
-            if constexpr (i >= 2 && i <= 5) st_a(i - 2);
+            if constexpr (i >= 4) st_a(i - 4);
             if constexpr (i == 6) st_b(0);
             if constexpr (i == 7) st_b(2);
-            if constexpr (i >= 1 && i <= 4) X = rdA[(i - 1) * 64];
+            if constexpr (i >= 3 && i <= 6) XA = rdA[(i - 3) * 64];
             if constexpr (i == 5 || i == 7) X = rdB[0];
             if constexpr (i == 6) X = rdB[64];
             EF_PIN();
@@ -720,19 +869,39 @@ __global__ __launch_bounds__(256, 1) void EF_KERNEL(const float *__restrict__ xy
             }
         }
     };
-    ef_layer<MT, EC_C3 / 32, EC_C4 / 32, true, false, true, PLANES, decltype(hook) &, true, false>(
+    // The parked values (layers 1-3: 16 per lane, complete once pair 0 has finished layer 3's last pair) take their way out behind
+    // the MFMAs of pairs 1 and 2, 16 execution steps of 3 MT slots: values 2 e and 2 e + 1 run their five stages at steps e .. e + 4,
+    // every stage in a gap of its own.
+    EfStage stg[(EC_C1 + EC_C2 + EC_C3) / 16];
+    auto unpark = [&](auto ic, auto sc) {
+        constexpr int i = decltype(ic)::value, slot = decltype(sc)::value;
+        if constexpr (PLANES && (i == 1 || i == 2)) {
+            constexpr int step = (i - 1) * 2 * (EC_C3 / 32) + slot / (3 * MT), pos = slot % (3 * MT);
+            // (stage, value parity) -> slot of the step: 1 2 3 4 6 | 7 8 9 11 0 -- below 3 MT for MT = 4 too, and not 5 or 10, where
+            // the layer-4 pair's own two values ride (ef_pair); the last stage of the odd values shares slot 0 with the fragment reads
+            static_assert(3 * MT >= 12, "ten stage slots and two of ef_pair's in a step");
+            constexpr int pi = pos == 1 ? 0 : pos == 2 ? 1 : pos == 3 ? 2 : pos == 4 ? 3 : pos == 6 ? 4
+                             : pos == 7 ? 5 : pos == 8 ? 6 : pos == 9 ? 7 : pos == 11 ? 8 : pos == 0 ? 9 : -1;
+            if constexpr (pi >= 0) {
+                constexpr int g = pi % 5, e = step - g, w = 2 * e + pi / 5;
+                if constexpr (e >= 0 && e < (EC_C1 + EC_C2 + EC_C3) / 32)
+                    ef_unpark<g, true>(stg[w], O.park[w], w < 4 ? s1.pool : w < 8 ? s2.pool : s3.pool, L.mres, O.ovf, L.stgA + 128 * w);
+            }
+        }
+    };
+    ef_layer<MT, EC_C3 / 32, EC_C4 / 32, true, false, true, PLANES, decltype(hook) &, true, false, decltype(unpark) &>(
         p3, dummy, w4, bs4, EfNext{w2, bs2, 0, 2 * (EC_C1 / 32)}, R, EC_C1 + EC_C2 + EC_C3, accA, accB,
-        EC_C1 + EC_C2 + 32 * (EC_C3 / 32 - 1), &mp_last, L, 0, s3, s4, ovf, hook);
+        EC_C1 + EC_C2 + 32 * (EC_C3 / 32 - 1), &mp_last, L, 0, s3, s4, O, hook, unpark);
     if constexpr (PLANES) st_b(4);                              // pairs 4, 5 (read before pair 7)
     asm volatile("s_nop 15\n\ts_nop 15");                       // the last asm MFMAs must have written accB (no compiler padding)
-    ef_finish_all<MT, true, true, PLANES>(accB, dummy[0], EC_C1 + EC_C2 + EC_C3 + 32 * mp_last, L, s4, ovf);
+    ef_finish_all<MT, true, true, PLANES>(accB, dummy[0], EC_C1 + EC_C2 + EC_C3 + 32 * mp_last, L, s4, O);
     if constexpr (PLANES) { X = rdB[64]; st_b(6); }             // pairs 6, 7
     EF_T(5);
     }
     // fp16 range guard: ovf = the largest value (in plane units) this lane handed to fp16 planes -- layers 1-3, and the
     // pooled planes when PLANES; activations are post-ReLU, so the pooled maxima are the maxima.  Not taken while the
     // activations stay within 16x of the magnitude the packer was told; the host re-runs on the bf16x3 kernel if it is.
-    if (!(ovf <= 60000.f) && range_flag) *(volatile int *)range_flag = 1; // may live in mapped host memory: plain store
+    if (!(O.ovf <= 60000.f) && range_flag) *(volatile int *)range_flag = 1; // may live in mapped host memory: plain store
 }
 
 // workgroups to launch: one per CU (persistent), or one per tile
