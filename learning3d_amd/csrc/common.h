@@ -28,6 +28,29 @@ static inline int l3d_check_launch() {
 
 static inline int l3d_divup(long a, long b) { return (int)((a + b - 1) / b); }
 
+typedef float f32x4 __attribute__((ext_vector_type(4)));       // an MFMA accumulator tile; 16 bytes of a row in one load or store
+
+// sum over the wave (double or float), every lane receiving it: an xor butterfly, so the order is fixed by the lane numbers and
+// every lane ends with the same bits
+template <typename T>
+__device__ __forceinline__ T l3d_wave_sum(T v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// sum over a workgroup of 256 threads in a fixed order, every thread receiving it; sRed: 4 doubles.  (train.hip's and svd.hip's
+// block sums associate otherwise and give other bits: they are not this function.)
+__device__ __forceinline__ double l3d_block_sum(double v, double *sRed)
+{
+    v = l3d_wave_sum(v);
+    __syncthreads();                                   // the previous sum's readers are done with sRed
+    if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((sRed[0] + sRed[1]) + sRed[2]) + sRed[3];
+}
+
 // sizes of the f16x2 plane images (conv_f16.hip; exported as l3d_f16_image_bytes(kind, rows, cols))
 static inline size_t l3d_f16_plane_bytes(long rows, int cols) { return (size_t)((cols + 7) / 8) * (size_t)rows * 16; }   // one plane, tiled layout
 static inline size_t l3d_f16_act_bytes(long rows, int cols) { return 2 * l3d_f16_plane_bytes(rows, cols) + 16; }         // h | m' + {2^-T, scratch}

@@ -17,13 +17,6 @@
 #define CW_MAX_LDS 65536      // dynamic LDS of the walk: curve_num (2 C + 3) words
 #define CP_TILE 64           // points per workgroup of the prepare kernel
 
-__device__ __forceinline__ float cw_wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);       // a butterfly: every lane ends with the same bits
-    return v;
-}
-
 // One workgroup walks all curves of one cloud, a wavefront per curve (curve q on wave q % CW_WAVES).  The curves of a cloud are NOT
 // independent: the reference views the momentum softmax [bs,2,n] as [bs,1,n,2] (:147) without transposing it, so curve q blends with
 // the values at flat positions 2 q and 2 q + 1 of its cloud's [2][n] array -- two OTHER curves' outputs.  Hence a barrier per step:
@@ -72,7 +65,7 @@ __global__ __launch_bounds__(CW_WAVES * 64) void curve_walk_kernel(const float *
                     p0 += w_m[c1] * cu + w_m[C + c1] * pr;
                     p1 += w_m[2 * C + c1] * cu + w_m[3 * C + c1] * pr;
                 }
-                const float m0 = sm0 * cw_wave_sum(p0) + hm0, m1 = sm1 * cw_wave_sum(p1) + hm1;
+                const float m0 = sm0 * l3d_wave_sum(p0) + hm0, m1 = sm1 * l3d_wave_sum(p1) + hm1;
                 const float mx = fmaxf(m0, m1), e0 = expf(m0 - mx), e1 = expf(m1 - mx), den = e0 + e1;
                 if (lane == 0) { sSm[q] = e0 / den; sSm[n + q] = e1 / den; }
             }
@@ -90,10 +83,10 @@ __global__ __launch_bounds__(CW_WAVES * 64) void curve_walk_kernel(const float *
                 if (has0) sPre[q * C + c0] = pre0;
                 if (has1) sPre[q * C + c1] = pre1;
                 const float d0 = cur0 - pre0, d1 = cur1 - pre1;
-                n1sq = cw_wave_sum(d0 * d0 + d1 * d1);
+                n1sq = l3d_wave_sum(d0 * d0 + d1 * d1);
             }
             // the descriptor's half of the agent's logit is the same for every candidate
-            const float pp = cw_wave_sum((has0 ? w_a[C + c0] * pre0 : 0.f) + (has1 ? w_a[C + c1] * pre1 : 0.f));
+            const float pp = l3d_wave_sum((has0 ? w_a[C + c0] * pre0 : 0.f) + (has1 ? w_a[C + c1] * pre1 : 0.f));
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");            // this wave's LDS writes above, read by all its lanes below
             const int at = sPt[q];
 

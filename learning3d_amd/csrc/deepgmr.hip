@@ -15,14 +15,6 @@
 #include "svd3x3.h"
 #include "../../include/models/l3d_deepgmr.h"
 
-// sum over the wave, every lane receiving it; the order is fixed by the lane numbers
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------------
 #define RRI_THREADS 256
 #define RRI_TWO_PI 6.283185307179586476925286766559
@@ -148,7 +140,7 @@ __global__ __launch_bounds__(TN) void gmm_params_kernel(const float *__restrict_
                         const double g = sG[j * TN + i];
                         a0 += g; a1 += g * sP[i * 3]; a2 += g * sP[i * 3 + 1]; a3 += g * sP[i * 3 + 2];
                     }
-                    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3);
+                    a0 = l3d_wave_sum(a0); a1 = l3d_wave_sum(a1); a2 = l3d_wave_sum(a2); a3 = l3d_wave_sum(a3);
                     if (lane == 0) { sAcc[j * 4] += a0; sAcc[j * 4 + 1] += a1; sAcc[j * 4 + 2] += a2; sAcc[j * 4 + 3] += a3; }
                 } else {
                     const double mx = sMu[j * 3], my = sMu[j * 3 + 1], mz = sMu[j * 3 + 2];
@@ -157,7 +149,7 @@ __global__ __launch_bounds__(TN) void gmm_params_kernel(const float *__restrict_
                         const double dx = sP[i * 3] - mx, dy = sP[i * 3 + 1] - my, dz = sP[i * 3 + 2] - mz;
                         a0 += (double)sG[j * TN + i] * ((dx * dx + dy * dy) + dz * dz);
                     }
-                    a0 = wave_sum(a0);
+                    a0 = l3d_wave_sum(a0);
                     if (lane == 0) sVar[j] += a0;
                 }
             }
@@ -210,14 +202,14 @@ __global__ __launch_bounds__(64) void gmm_register_kernel(const float *__restric
     }
 #pragma unroll
     for (int d = 0; d < 3; d++) {
-        c[d] = wave_sum(in ? w * ms[d] : 0.0);
-        c[3 + d] = wave_sum(in ? w * mt[d] : 0.0);
+        c[d] = l3d_wave_sum(in ? w * ms[d] : 0.0);
+        c[3 + d] = l3d_wave_sum(in ? w * mt[d] : 0.0);
     }
     double h[9];
 #pragma unroll
     for (int r = 0; r < 3; r++)
 #pragma unroll
-        for (int q = 0; q < 3; q++) h[r * 3 + q] = wave_sum(in ? w * (ms[r] - c[r]) * (mt[q] - c[3 + q]) * iv : 0.0);
+        for (int q = 0; q < 3; q++) h[r * 3 + q] = l3d_wave_sum(in ? w * (ms[r] - c[r]) * (mt[q] - c[3 + q]) * iv : 0.0);
     if (lane == 0) {
         float r[9];
         rotation_from_H(h, r);

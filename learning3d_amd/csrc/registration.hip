@@ -91,16 +91,6 @@ extern "C" int l3d_reg_pose_first_layer(const float *cloud, const float *T, cons
 }
 
 // ---------------------------------------------------------------------------------------------
-// sums over the workgroup (fp64), every thread receiving the total
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double reg_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// ---------------------------------------------------------------------------------------------
 // Jacobian -> pseudo-inverse, one workgroup per cloud.  The 6 x 12 augmented matrix [H | I] lives in LDS; thread (r, c) of the
 // first 72 owns one element, so no thread indexes a private array.
 // ---------------------------------------------------------------------------------------------
@@ -133,7 +123,7 @@ __global__ __launch_bounds__(REG_THREADS) void reg_jac_pinv_kernel(const float *
     }
 #pragma unroll
     for (int i = 0; i < 21; i++) {
-        const double s = reg_wave_sum(h[i]);
+        const double s = l3d_wave_sum(h[i]);
         if ((tid & 63) == 0) sH[tid >> 6][i] = s;
     }
     if (tid == 0) sSing = 0;
@@ -263,7 +253,7 @@ __global__ __launch_bounds__(REG_THREADS) void reg_iclk_step_kernel(const float 
     }
 #pragma unroll
     for (int k = 0; k < 6; k++) {
-        const double s = reg_wave_sum(acc[k]);
+        const double s = l3d_wave_sum(acc[k]);
         if ((tid & 63) == 0) sAcc[tid >> 6][k] = s;
     }
     __syncthreads();

@@ -6,35 +6,16 @@
 //   l3d_gn_conv        1x1 convolution whose operand is the previous GroupNorm + ReLU applied on load and whose epilogue sums the
 //                      next GroupNorm's raw moments (fp64) and, pooled, keeps the maximum and minimum over the K neighbours: the
 //                      [B,C,K,N] activations of the pre-pool stack are read once and written at most once per layer, the last one
-//                      never.  A workgroup owns 64 output channels (a 16-row MFMA tile per wave) and walks blocks of 64 positions;
-//                      input channels go through LDS in chunks of 64, zero-padded there.
-//   l3d_gn_affine      moments -> the per-(cloud, channel) scale and shift of the GroupNorm.
+//                      never.  A workgroup owns 64 output channels and walks blocks of 64 positions; the tile itself is gn_tile
+//                      (gn_tile.h), which rpmnet_param.hip's kernels call too; the epilogue is this file's.
+//   l3d_gn_affine      moments -> the per-(cloud, channel) scale and shift of the GroupNorm (the group's mean and rstd: gn_tile.h).
 //   l3d_sinkhorn_slack the slack Sinkhorn as two potentials: a row pass (a wave per row), a column pass (64 columns per workgroup,
 //                      4 row slices merged through LDS) and one output pass.  One-pass logsumexp in fp64.
 //   l3d_rigid_transform_weighted   weighted Kabsch, one workgroup per cloud, the 3x3 SVD of svd3x3.h in thread 0.
 #include "common.h"
+#include "gn_tile.h"
 #include "svd3x3.h"
 #include "../../include/ext/l3d_rpmnet.h"
-
-typedef float rp_f32x4 __attribute__((ext_vector_type(4)));
-
-// sum over the wave, every lane receiving it; the order is fixed by the lane numbers
-__device__ __forceinline__ double rp_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// sum over the workgroup (256 threads) in a fixed order, every thread receiving it; sRed: 4 doubles
-__device__ __forceinline__ double rp_block_sum(double v, double *sRed)
-{
-    v = rp_wave_sum(v);
-    __syncthreads();                                   // the previous sum's readers are done with sRed
-    if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sRed[0] + sRed[1]) + sRed[2]) + sRed[3];
-}
 
 // ------------------------------------------------------------------------------------------------------------------------------
 #define PPF_THREADS 256
@@ -81,11 +62,6 @@ extern "C" int l3d_ppf_group(const float *xyz, const float *normals, const int64
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-#define GC_TP 64                // positions per block
-#define GC_TC 64                // input channels per LDS chunk
-#define GC_LDU 80               // row pitch of the operand tile: the four k rows of an MFMA step land 16 banks apart
-#define GC_LDW 65               // row pitch of the weight tile: 16 consecutive rows on 16 different banks
-
 struct GcPlan {
     int K, NP, nblocks, bpp, nparts;
 };
@@ -95,7 +71,7 @@ static GcPlan gc_plan(int P, int pool)
     GcPlan g;
     g.K = pool > 0 ? pool : 1;
     g.NP = P / g.K;
-    g.nblocks = l3d_divup(g.NP, GC_TP);
+    g.nblocks = l3d_divup(g.NP, GN_TP);
     g.bpp = l3d_divup(g.nblocks, L3D_GN_CONV_PARTS);
     g.nparts = l3d_divup(g.nblocks, g.bpp);
     return g;
@@ -108,31 +84,23 @@ __global__ __launch_bounds__(256) void gn_conv_kernel(const float *__restrict__ 
                                                       int nblocks, int bpp, int nparts, float *__restrict__ y,
                                                       float *__restrict__ ymax, float *__restrict__ ymin, double *__restrict__ partials)
 {
-    __shared__ float sW[GC_TC * GC_LDW];               // [co][ci]
-    __shared__ float sU[GC_TC * GC_LDU];               // [ci][position]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, m = lane & 15;
-    const int part = blockIdx.x, co0 = blockIdx.y * 64, b = blockIdx.z;
-    const int cow = co0 + wave * 16;                   // this wave's row tile
-    const bool wave_on = cow < Cout;                   // Cout % 16 == 0: a tile is whole or absent
+    __shared__ float sW[GN_TC * GN_LDW];               // [co][ci]
+    __shared__ float sU[GN_TC * GN_LDU];               // [ci][position]
+    const GnCtx cx = gn_ctx(Cin, Cout);
+    const int part = blockIdx.x, b = cx.b, cow = cx.cow, g = cx.g, m = cx.m;
+    const bool wave_on = cx.wave_on;
     const float *xb = x + (size_t)b * Cin * P;
-    const bool w_once = Cin <= GC_TC;
-    const int nchunks = (Cin + GC_TC - 1) / GC_TC;
 
     float bv[4];
 #pragma unroll
     for (int r = 0; r < 4; r++) bv[r] = (wave_on && bias) ? bias[cow + 4 * g + r] : 0.f;
     double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
 
-    if (w_once) {
-        for (int e = tid; e < GC_TC * GC_TC; e += 256) {
-            const int row = e >> 6, col = e & 63;
-            sW[row * GC_LDW + col] = (co0 + row < Cout && col < Cin) ? w[(size_t)(co0 + row) * Cin + col] : 0.f;
-        }
-    }
+    gn_weights_once(cx, w, Cin, Cout, sW);
 
     const int cb_end = min((part + 1) * bpp, nblocks);
     for (int cb = part * bpp; cb < cb_end; cb++) {
-        const int c0 = cb * GC_TP;
+        const int c0 = cb * GN_TP;
         float mx[4][4], mn[4][4];
 #pragma unroll
         for (int t = 0; t < 4; t++)
@@ -140,41 +108,8 @@ __global__ __launch_bounds__(256) void gn_conv_kernel(const float *__restrict__ 
             for (int r = 0; r < 4; r++) { mx[t][r] = -INFINITY; mn[t][r] = INFINITY; }
 
         for (int k = 0; k < K; k++) {
-            const size_t p0 = (size_t)k * NP + c0;
-            rp_f32x4 acc[4];
-#pragma unroll
-            for (int t = 0; t < 4; t++) acc[t] = rp_f32x4{bv[0], bv[1], bv[2], bv[3]};
-
-            for (int ch = 0; ch < nchunks; ch++) {
-                const int ci0 = ch * GC_TC, cn = min(GC_TC, Cin - ci0);
-                __syncthreads();                       // the previous tile's MFMA reads are done
-                if (!w_once) {
-                    for (int e = tid; e < GC_TC * GC_TC; e += 256) {
-                        const int row = e >> 6, col = e & 63;
-                        sW[row * GC_LDW + col] = (co0 + row < Cout && col < cn) ? w[(size_t)(co0 + row) * Cin + ci0 + col] : 0.f;
-                    }
-                }
-                const int cn4 = (cn + 3) & ~3;         // rows up to the next multiple of 4 are read by the last MFMA step: zeros
-                for (int e = tid; e < cn4 * GC_TP; e += 256) {
-                    const int ci = e >> 6, j = e & 63;
-                    float u = 0.f;
-                    if (ci < cn && c0 + j < NP) {
-                        u = xb[(size_t)(ci0 + ci) * P + p0 + j];
-                        if (in_a) u = fmaxf(fmaf(in_a[(size_t)b * Cin + ci0 + ci], u, in_s[(size_t)b * Cin + ci0 + ci]), 0.f);
-                    }
-                    sU[ci * GC_LDU + j] = u;
-                }
-                __syncthreads();
-                if (wave_on) {
-                    const int steps = cn4 >> 2;
-                    for (int s = 0; s < steps; s++) {
-                        const float a = sW[(wave * 16 + m) * GC_LDW + 4 * s + g];
-                        const float *ur = sU + (4 * s + g) * GC_LDU + m;
-#pragma unroll
-                        for (int t = 0; t < 4; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, ur[16 * t], acc[t], 0, 0, 0);
-                    }
-                }
-            }
+            f32x4 acc[4];
+            gn_tile(cx, xb, in_a, in_s, w, bv, Cin, Cout, P, (size_t)k * NP + c0, c0, NP, sW, sU, acc);
 
             // acc[t][r] = output channel cow + 4 g + r at column c0 + 16 t + m of level k
             if (wave_on) {
@@ -247,7 +182,7 @@ __global__ __launch_bounds__(256) void gn_moments_kernel(const double *__restric
 extern "C" size_t l3d_gn_conv_workspace_bytes(int B, int Cout, int P)
 {
     if (B <= 0 || Cout <= 0 || P <= 0) return 0;
-    const long blocks = l3d_divup(P, GC_TP), parts = blocks < L3D_GN_CONV_PARTS ? blocks : L3D_GN_CONV_PARTS;      // pooled or not, never more than this
+    const long blocks = l3d_divup(P, GN_TP), parts = blocks < L3D_GN_CONV_PARTS ? blocks : L3D_GN_CONV_PARTS;      // pooled or not, never more than this
     return (size_t)B * Cout * parts * 2 * sizeof(double);
 }
 
@@ -279,18 +214,8 @@ __global__ __launch_bounds__(64) void gn_affine_kernel(const double *__restrict_
                                                        float *__restrict__ a, float *__restrict__ s)
 {
     const int lane = threadIdx.x, grp = blockIdx.x, b = blockIdx.y, cpg = C / groups;
-    double m1 = 0.0, m2 = 0.0;
-    for (int c = lane; c < cpg; c += 64) {
-        const double *mo = moments + ((size_t)b * C + grp * cpg + c) * 2;
-        m1 += mo[0];
-        m2 += mo[1];
-    }
-    m1 = rp_wave_sum(m1);
-    m2 = rp_wave_sum(m2);
-    const double n = count * cpg, mean = m1 / n;
-    double var = m2 / n - mean * mean;
-    var = var < 0.0 ? 0.0 : var;
-    const double rstd = 1.0 / sqrt(var + eps);
+    double mean, rstd;
+    gn_group_stats(moments, b, C, groups, grp, lane, count, eps, mean, rstd);
     for (int c = lane; c < cpg; c += 64) {
         const int ch = grp * cpg + c;
         const double av = (double)gamma[ch] * rstd;
@@ -414,10 +339,10 @@ __global__ __launch_bounds__(256) void sk_out_kernel(const float *__restrict__ A
         }
     }
     if (rowsum || weighted) {
-        rs = rp_wave_sum(rs);
+        rs = l3d_wave_sum(rs);
         if (rowsum && lane == 0) rowsum[(size_t)b * J + j] = (float)rs;
         if (weighted) {
-            wx = rp_wave_sum(wx); wy = rp_wave_sum(wy); wz = rp_wave_sum(wz);
+            wx = l3d_wave_sum(wx); wy = l3d_wave_sum(wy); wz = l3d_wave_sum(wz);
             if (lane == 0) {
                 // the reference divides by the fp32 row sum plus eps
                 const double den = (double)(float)rs + eps;
@@ -471,7 +396,7 @@ __global__ __launch_bounds__(256) void rigid_weighted_kernel(const float *__rest
         }
     }
 #pragma unroll
-    for (int q = 0; q < 7; q++) acc[q] = rp_block_sum(acc[q], sRed);
+    for (int q = 0; q < 7; q++) acc[q] = l3d_block_sum(acc[q], sRed);
     const double inv = 1.0 / (acc[0] + eps);
     double ca[3], cb[3];
 #pragma unroll
@@ -488,7 +413,7 @@ __global__ __launch_bounds__(256) void rigid_weighted_kernel(const float *__rest
             for (int q = 0; q < 3; q++) h[r * 3 + q] += da[r] * db[q];
     }
 #pragma unroll
-    for (int q = 0; q < 9; q++) h[q] = rp_block_sum(h[q], sRed);
+    for (int q = 0; q < 9; q++) h[q] = l3d_block_sum(h[q], sRed);
     if (tid == 0) {
         float r[9];
         rotation_from_H(h, r);

@@ -13,16 +13,6 @@
 #include "common.h"
 #include "../../include/ext/l3d_rpmnet_match.h"
 
-typedef float mt_f32x4 __attribute__((ext_vector_type(4)));
-
-// sum over the wave, every lane receiving it; the order is fixed by the lane numbers
-__device__ __forceinline__ double mt_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // running logsumexp, as rpmnet.hip's: (m, s) stands for m + log(s); the empty state is (-inf, 0)
 struct MtLse {
     double m, s;
@@ -54,7 +44,7 @@ template <int W>
 __device__ __forceinline__ void mt_load(float (&d)[W], const float *__restrict__ p)
 {
     if constexpr (W == 4) {
-        const mt_f32x4 t = *reinterpret_cast<const mt_f32x4 *>(p);
+        const f32x4 t = *reinterpret_cast<const f32x4 *>(p);
         d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
     } else {
         d[0] = p[0];
@@ -65,9 +55,9 @@ template <int W>
 __device__ __forceinline__ void mt_store(float *__restrict__ p, const float (&d)[W])
 {
     if constexpr (W == 4) {
-        mt_f32x4 t;
+        f32x4 t;
         t.x = d[0]; t.y = d[1]; t.z = d[2]; t.w = d[3];
-        *reinterpret_cast<mt_f32x4 *>(p) = t;
+        *reinterpret_cast<f32x4 *>(p) = t;
     } else {
         p[0] = d[0];
     }
@@ -148,10 +138,10 @@ __global__ __launch_bounds__(256) void mt_fwd_out_kernel(const float *__restrict
         }
     }
     if (rowsum || weighted) {
-        rs = mt_wave_sum(rs);
+        rs = l3d_wave_sum(rs);
         if (rowsum && lane == 0) rowsum[(size_t)b * J + j] = (float)rs;
         if (weighted) {
-            wx = mt_wave_sum(wx); wy = mt_wave_sum(wy); wz = mt_wave_sum(wz);
+            wx = l3d_wave_sum(wx); wy = l3d_wave_sum(wy); wz = l3d_wave_sum(wz);
             if (lane == 0) {
                 const double den = (double)(float)rs + eps;
                 float *o = weighted + ((size_t)b * J + j) * 3;
@@ -219,11 +209,11 @@ __global__ __launch_bounds__(256) void mt_bwd_first_row_kernel(const float *__re
             }
         }
     }
-    r = mt_wave_sum(r);
+    r = l3d_wave_sum(r);
     const double den = r + eps;
     double gx = 0.0, gy = 0.0, gz = 0.0, c0 = 0.0;
     if (want_x) {
-        px = mt_wave_sum(px); py = mt_wave_sum(py); pz = mt_wave_sum(pz);
+        px = l3d_wave_sum(px); py = l3d_wave_sum(py); pz = l3d_wave_sum(pz);
         const float *dw = d_weighted + rj * 3;
         gx = (double)dw[0] / den; gy = (double)dw[1] / den; gz = (double)dw[2] / den;
         c0 = -((gx * (px / den) + gy * (py / den)) + gz * (pz / den));
@@ -247,7 +237,7 @@ __global__ __launch_bounds__(256) void mt_bwd_first_row_kernel(const float *__re
             sg += p * t;
         }
     }
-    sg = mt_wave_sum(sg);
+    sg = l3d_wave_sum(sg);
     if (lane == 0) {
         double *st = rowstat + rj * 4;
         st[0] = c0; st[1] = gx; st[2] = gy; st[3] = gz;
@@ -307,7 +297,7 @@ __global__ __launch_bounds__(256) void mt_bwd_row_kernel(const float *__restrict
 #pragma unroll
         for (int i = 0; i < W; i++) acc += vbb[k0 + i] * exp(((double)a[i] - uj) - vb[k0 + i]);
     }
-    acc = mt_wave_sum(acc);
+    acc = l3d_wave_sum(acc);
     if (lane == 0) ubar[rj] = (init ? init[rj] : 0.0) - acc;
 }
 
@@ -398,8 +388,8 @@ __global__ __launch_bounds__(256) void mt_bwd_out_kernel(const float *__restrict
         mt_store<W>(d_out + at + k0, o);
     }
     if (part) {
-        s1 = mt_wave_sum(s1);
-        s2 = mt_wave_sum(s2);
+        s1 = l3d_wave_sum(s1);
+        s2 = l3d_wave_sum(s2);
         if (lane == 0) {
             part[rj * 2] = s1;
             part[rj * 2 + 1] = s2;

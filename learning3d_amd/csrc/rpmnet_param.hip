@@ -5,20 +5,12 @@
 //   l3d_gn_conv_gpool      y tile by tile; per (cloud, channel) the extremes of y over all positions, the lowest position of each
 //                          and the GroupNorm's raw moments (fp64): per-workgroup partials, a second launch in ascending order
 //   l3d_gn_gpool_backward  y again; dz = rstd (gamma g [p == winner] - M1 - zhat M2) in fp64, rounded once, dense [B,Cout,P]
-// Both form y on l3d_gn_conv's tile (rpmnet.hip: a workgroup owns 64 output channels, a 16-row MFMA tile per wave, and walks blocks
-// of 64 positions; input channels through LDS in chunks of 64, zero-padded there) by gp_tile below, which is gn_conv_kernel's
-// accumulation statement for statement: the accumulator starts at the bias and takes v_mfma_f32_16x16x4_f32 steps in ascending
-// ci over the operand transformed on load, so y is l3d_gn_conv(pool = 0)'s, bit for bit.
+// Both form y by gn_tile (gn_tile.h), the tile l3d_gn_conv's kernel (rpmnet.hip) calls too, so y is l3d_gn_conv(pool = 0)'s, bit for
+// bit; the epilogues are this file's.
 #include "common.h"
+#include "gn_tile.h"
 #include "../../include/ext/l3d_rpmnet.h"
 #include "../../include/ext/l3d_rpmnet_param.h"
-
-typedef float gp_f32x4 __attribute__((ext_vector_type(4)));
-
-#define GP_TP 64                // positions per block
-#define GP_TC 64                // input channels per LDS chunk
-#define GP_LDU 80               // row pitch of the operand tile: the four k rows of an MFMA step land 16 banks apart
-#define GP_LDW 65               // row pitch of the weight tile: 16 consecutive rows on 16 different banks
 
 struct GpPlan {
     int nblocks, bpp, nparts;
@@ -27,84 +19,10 @@ struct GpPlan {
 static GpPlan gp_plan(int P)
 {
     GpPlan g;
-    g.nblocks = l3d_divup(P, GP_TP);
+    g.nblocks = l3d_divup(P, GN_TP);
     g.bpp = l3d_divup(g.nblocks, L3D_GN_GPOOL_PARTS);
     g.nparts = l3d_divup(g.nblocks, g.bpp);
     return g;
-}
-
-// what a workgroup of either kernel knows of itself
-struct GpCtx {
-    int tid, lane, wave, g, m, co0, cow, b, nchunks;
-    bool wave_on, w_once;
-};
-
-__device__ __forceinline__ GpCtx gp_ctx(int Cin, int Cout)
-{
-    GpCtx c;
-    c.tid = threadIdx.x;
-    c.lane = c.tid & 63;
-    c.wave = c.tid >> 6;
-    c.g = c.lane >> 4;
-    c.m = c.lane & 15;
-    c.co0 = blockIdx.y * 64;
-    c.b = blockIdx.z;
-    c.cow = c.co0 + c.wave * 16;                       // this wave's row tile
-    c.wave_on = c.cow < Cout;                          // Cout % 16 == 0: a tile is whole or absent
-    c.w_once = Cin <= GP_TC;
-    c.nchunks = (Cin + GP_TC - 1) / GP_TC;
-    return c;
-}
-
-// the whole weight tile of a workgroup whose Cin fits one chunk: loaded once, in front of the first block
-__device__ __forceinline__ void gp_weights_once(const GpCtx &c, const float *__restrict__ w, int Cin, int Cout, float *sW)
-{
-    if (!c.w_once) return;
-    for (int e = c.tid; e < GP_TC * GP_TC; e += 256) {
-        const int row = e >> 6, col = e & 63;
-        sW[row * GP_LDW + col] = (c.co0 + row < Cout && col < Cin) ? w[(size_t)(c.co0 + row) * Cin + col] : 0.f;
-    }
-}
-
-// acc[t][r] = y of output channel cow + 4 g + r at position c0 + 16 t + m, for the block of 64 positions at c0.  Every thread of the
-// workgroup calls it (it synchronises); columns at or past P hold the bias alone and are the caller's to leave out.
-__device__ __forceinline__ void gp_tile(const GpCtx &c, const float *__restrict__ xb, const float *__restrict__ in_a,
-                                        const float *__restrict__ in_s, const float *__restrict__ w, const float (&bv)[4], int Cin,
-                                        int Cout, int P, int c0, float *sW, float *sU, gp_f32x4 (&acc)[4])
-{
-#pragma unroll
-    for (int t = 0; t < 4; t++) acc[t] = gp_f32x4{bv[0], bv[1], bv[2], bv[3]};
-
-    for (int ch = 0; ch < c.nchunks; ch++) {
-        const int ci0 = ch * GP_TC, cn = min(GP_TC, Cin - ci0);
-        __syncthreads();                               // the previous tile's MFMA reads are done
-        if (!c.w_once) {
-            for (int e = c.tid; e < GP_TC * GP_TC; e += 256) {
-                const int row = e >> 6, col = e & 63;
-                sW[row * GP_LDW + col] = (c.co0 + row < Cout && col < cn) ? w[(size_t)(c.co0 + row) * Cin + ci0 + col] : 0.f;
-            }
-        }
-        const int cn4 = (cn + 3) & ~3;                 // rows up to the next multiple of 4 are read by the last MFMA step: zeros
-        for (int e = c.tid; e < cn4 * GP_TP; e += 256) {
-            const int ci = e >> 6, j = e & 63;
-            float u = 0.f;
-            if (ci < cn && c0 + j < P) {
-                u = xb[(size_t)(ci0 + ci) * P + c0 + j];
-                if (in_a) u = fmaxf(fmaf(in_a[(size_t)c.b * Cin + ci0 + ci], u, in_s[(size_t)c.b * Cin + ci0 + ci]), 0.f);
-            }
-            sU[ci * GP_LDU + j] = u;
-        }
-        __syncthreads();
-        if (c.wave_on) {
-            const int steps = cn4 >> 2;
-            for (int s = 0; s < steps; s++) {
-                const float a = sW[(c.wave * 16 + c.m) * GP_LDW + 4 * s + c.g];
-                const float *ur = sU + (4 * s + c.g) * GP_LDU + c.m;
-#pragma unroll
-                for (int t = 0; t < 4; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, ur[16 * t], acc[t], 0, 0, 0);
-            }
-        }
-    }
 }
 
 // (value, position) of a maximum / minimum: the better value, the lower position between equal values (-0 == +0)
@@ -131,9 +49,9 @@ __global__ __launch_bounds__(256) void gn_conv_gpool_kernel(const float *__restr
                                                             int bpp, int nparts, double *__restrict__ sums, float *__restrict__ ext,
                                                             int *__restrict__ pos)
 {
-    __shared__ float sW[GP_TC * GP_LDW];               // [co][ci]
-    __shared__ float sU[GP_TC * GP_LDU];               // [ci][position]
-    const GpCtx c = gp_ctx(Cin, Cout);
+    __shared__ float sW[GN_TC * GN_LDW];               // [co][ci]
+    __shared__ float sU[GN_TC * GN_LDU];               // [ci][position]
+    const GnCtx c = gn_ctx(Cin, Cout);
     const int part = blockIdx.x;
     const float *xb = x + (size_t)c.b * Cin * P;
 
@@ -146,13 +64,13 @@ __global__ __launch_bounds__(256) void gn_conv_gpool_kernel(const float *__restr
 #pragma unroll
     for (int r = 0; r < 4; r++) { mx[r] = -INFINITY; mn[r] = INFINITY; px[r] = pn[r] = 0x7fffffff; }
 
-    gp_weights_once(c, w, Cin, Cout, sW);
+    gn_weights_once(c, w, Cin, Cout, sW);
 
     const int cb_end = min((part + 1) * bpp, nblocks);
     for (int cb = part * bpp; cb < cb_end; cb++) {
-        const int c0 = cb * GP_TP;
-        gp_f32x4 acc[4];
-        gp_tile(c, xb, in_a, in_s, w, bv, Cin, Cout, P, c0, sW, sU, acc);
+        const int c0 = cb * GN_TP;
+        f32x4 acc[4];
+        gn_tile(c, xb, in_a, in_s, w, bv, Cin, Cout, P, c0, c0, P, sW, sU, acc);
         if (c.wave_on) {
 #pragma unroll
             for (int t = 0; t < 4; t++) {
@@ -273,9 +191,9 @@ __global__ __launch_bounds__(256) void gn_gpool_backward_kernel(const float *__r
                                                                 int Cin, int Cout, int groups, int P, int nblocks, int bpp,
                                                                 float *__restrict__ dz)
 {
-    __shared__ float sW[GP_TC * GP_LDW];               // [co][ci]
-    __shared__ float sU[GP_TC * GP_LDU];               // [ci][position]
-    const GpCtx c = gp_ctx(Cin, Cout);
+    __shared__ float sW[GN_TC * GN_LDW];               // [co][ci]
+    __shared__ float sU[GN_TC * GN_LDU];               // [ci][position]
+    const GnCtx c = gn_ctx(Cin, Cout);
     const int part = blockIdx.x;
     const float *xb = x + (size_t)c.b * Cin * P;
 
@@ -301,13 +219,13 @@ __global__ __launch_bounds__(256) void gn_gpool_backward_kernel(const float *__r
         }
     }
 
-    gp_weights_once(c, w, Cin, Cout, sW);
+    gn_weights_once(c, w, Cin, Cout, sW);
 
     const int cb_end = min((part + 1) * bpp, nblocks);
     for (int cb = part * bpp; cb < cb_end; cb++) {
-        const int c0 = cb * GP_TP;
-        gp_f32x4 acc[4];
-        gp_tile(c, xb, in_a, in_s, w, bv, Cin, Cout, P, c0, sW, sU, acc);
+        const int c0 = cb * GN_TP;
+        f32x4 acc[4];
+        gn_tile(c, xb, in_a, in_s, w, bv, Cin, Cout, P, c0, c0, P, sW, sU, acc);
         if (c.wave_on) {
 #pragma unroll
             for (int t = 0; t < 4; t++) {

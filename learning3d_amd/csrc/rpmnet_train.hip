@@ -3,7 +3,7 @@
 // ReLU mask and the normalised value are recomputed here from y and the per-(cloud, channel) affine (in_a, in_s) as the forward's
 // l3d_gn_conv forms them on load: h = fmaf(in_a, y, in_s), one rounding.
 //
-//   l3d_gn_mean_rstd        moments -> (mean, rstd) per (cloud, group), the sums of l3d_gn_affine in the same order
+//   l3d_gn_mean_rstd        moments -> (mean, rstd) per (cloud, group) by gn_group_stats (gn_tile.h), as l3d_gn_affine forms them
 //   l3d_gn_pool_winner      the lowest k attaining the extreme in_a's sign selects; a lane per n, k rows read in runs along n
 //   l3d_gn_relu             u = max(0, h) written out: the second operand of the next layer's l3d_wgrad
 //   l3d_gn_backward_stats   (sum g, sum g zhat) per (cloud, channel): a workgroup per 8192-position chunk of a row, fp64, fixed order;
@@ -14,26 +14,9 @@
 // stats and apply stream [B,C,P] tensors and are HBM-bound: 16 bytes per lane where P (pooled: N') is a multiple of 4 and the pointers
 // allow, a scalar route otherwise; grids are (chunks, C, B), so B = 2 fills the machine as B = 32 does.  Nothing divides by gamma.
 #include "common.h"
+#include "gn_tile.h"
 #include "../../include/ext/l3d_rpmnet.h"
 #include "../../include/ext/l3d_rpmnet_train.h"
-
-// sum over the wave, every lane receiving it; the order is fixed by the lane numbers
-__device__ __forceinline__ double gt_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// sum over the workgroup (256 threads) in a fixed order, every thread receiving it; sRed: 4 doubles
-__device__ __forceinline__ double gt_block_sum(double v, double *sRed)
-{
-    v = gt_wave_sum(v);
-    __syncthreads();                                   // the previous sum's readers are done with sRed
-    if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sRed[0] + sRed[1]) + sRed[2]) + sRed[3];
-}
 
 static bool gt_aligned(const void *p, size_t to)
 {
@@ -41,26 +24,17 @@ static bool gt_aligned(const void *p, size_t to)
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// a wave per (cloud, group); the sums of gn_affine_kernel (rpmnet.hip), lane for lane
+// a wave per (cloud, group); gn_group_stats (gn_tile.h) is gn_affine_kernel's too
 __global__ __launch_bounds__(64) void gn_mean_rstd_kernel(const double *__restrict__ moments, int C, int groups, double count,
                                                           double eps, double *__restrict__ stat)
 {
-    const int lane = threadIdx.x, grp = blockIdx.x, b = blockIdx.y, cpg = C / groups;
-    double m1 = 0.0, m2 = 0.0;
-    for (int c = lane; c < cpg; c += 64) {
-        const double *mo = moments + ((size_t)b * C + grp * cpg + c) * 2;
-        m1 += mo[0];
-        m2 += mo[1];
-    }
-    m1 = gt_wave_sum(m1);
-    m2 = gt_wave_sum(m2);
-    const double n = count * cpg, mean = m1 / n;
-    double var = m2 / n - mean * mean;
-    var = var < 0.0 ? 0.0 : var;
+    const int lane = threadIdx.x, grp = blockIdx.x, b = blockIdx.y;
+    double mean, rstd;
+    gn_group_stats(moments, b, C, groups, grp, lane, count, eps, mean, rstd);
     if (lane == 0) {
         double *o = stat + ((size_t)b * groups + grp) * 2;
         o[0] = mean;
-        o[1] = 1.0 / sqrt(var + eps);
+        o[1] = rstd;
     }
 }
 
@@ -194,8 +168,8 @@ __global__ __launch_bounds__(256) void gn_backward_stats_kernel(const float *__r
             s2 += g * (((double)yv - r.mean) * r.rstd);
         }
     }
-    s1 = gt_block_sum(s1, sRed);
-    s2 = gt_block_sum(s2, sRed);
+    s1 = l3d_block_sum(s1, sRed);
+    s2 = l3d_block_sum(s2, sRed);
     if (tid == 0) {
         double *o = out + (row * nparts + part) * 2;
         o[0] = s1;

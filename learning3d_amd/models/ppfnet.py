@@ -193,6 +193,42 @@ def gn_backward(du, y, a, s, stat, gamma, groups, widx=None, K=0, want_gamma=Tru
     return dz, dgamma, dbeta
 
 
+def backward_descent(layers, ys, affs, stats, params, needs, slot, grads, dz, start, operand, pooled=None):
+    """The backward of a stack of conv -> GroupNorm -> ReLU layers from layer `start` down, shared by PPFNet._Train and
+    ParameterPredictionNet._Train.  layers: (conv, norm) pairs; ys[i], affs[2 i], affs[2 i + 1], stats[i]: layer i's convolution
+    output, a, s and (mean, rstd) as the forward kept them; params, needs, slot: the parameter tensors, which of them need a gradient,
+    and id(parameter) -> its place in both; grads: filled in place.  dz: a one-element list holding the gradient at layer `start`'s
+    convolution output, emptied here -- the caller keeps no other reference, so that the releases below hand the blocks back.
+    operand(i): the wgrad operand of layer i, the input its convolution loaded.  pooled = (index, widx, K): that layer's output went
+    through the maximum over K neighbours, widx its winner index.
+    Per layer: dW by l3d_wgrad on the operand (released behind the wgrad, so that the allocator hands the block to the layer below),
+    db as the first column of l3d_channel_stats summed over the clouds; it stops at the first layer, or where nothing underneath
+    learns; else du = W^T dz by l3d_gn_conv on the transposed weight, then gn_backward of the layer below."""
+    from ._train import channel_stats, sum_clouds, wgrad
+    dz = dz.pop()
+    for i in range(start, -1, -1):
+        conv, _ = layers[i]
+        jw, jb = slot[id(conv.weight)], slot.get(id(conv.bias))
+        if needs[jw]:
+            u = operand(i)
+            grads[jw] = wgrad(dz, u).view_as(conv.weight)
+            del u                                  # back to the allocator before du and dz of the layer below are made
+        if jb is not None and needs[jb]:
+            grads[jb] = sum_clouds(channel_stats(dz))[:, 0].float()
+        below = [p for pair in layers[:i] for m in pair for p in (m.weight, m.bias) if p is not None]
+        if not any(needs[slot[id(p)]] for p in below):
+            break                                  # the first layer, or nothing underneath learns
+        w = f32c(params[jw]).view(conv.out_channels, conv.in_channels)
+        du = gn_conv(dz, None, None, w.t().contiguous(), None)[0]
+        del dz                                     # (the widest one in either network: gone before the next is made)
+        norm = layers[i - 1][1]
+        jg, jt = slot[id(norm.weight)], slot[id(norm.bias)]
+        widx, K = pooled[1:] if pooled is not None and pooled[0] == i - 1 else (None, 0)
+        dz, grads[jg], grads[jt] = gn_backward(du, ys[i - 1], affs[2 * i - 2], affs[2 * i - 1], stats[i - 1], params[jg],
+                                               norm.num_groups, widx, K, want_gamma=needs[jg], want_beta=needs[jt])
+        del du
+
+
 _TLS = threading.local()
 
 
@@ -297,10 +333,8 @@ class PPFNet(nn.Module):
         idx, the convolution outputs y1..y5 (the three pre-pool ones are the only [B,C,K N] tensors), the pooled extreme [B,C,N],
         per layer a, s [B,C] and (mean, rstd) fp64 [B,8,2], and the winner index, one byte per [B,C,N].  No ReLU output, no
         normalised value and no fp64 tensor of activation size: the backward recomputes them from y, a, s.
-        backward, last layer to first: the wgrad operand max(0, fmaf(a, y, s)) of the layer below written by l3d_gn_relu and released
-        behind the wgrad, so that the allocator hands the block to the next layer (the first layer's operand is l3d_ppf_group again),
-        dW by l3d_wgrad, db as the first column of
-        l3d_channel_stats summed over the clouds, du = W^T dz by l3d_gn_conv on the transposed weight, then gn_backward."""
+        backward: backward_descent from the last layer; a layer's wgrad operand is max(0, fmaf(a, y, s)) of the layer below written by
+        l3d_gn_relu (the first layer's is l3d_ppf_group again)."""
 
         @staticmethod
         def forward(ctx, net, xyz, normals, *params):
@@ -333,7 +367,6 @@ class PPFNet(nn.Module):
         @staticmethod
         @torch.autograd.function.once_differentiable
         def backward(ctx, dout):
-            from ._train import channel_stats, sum_clouds, wgrad
             net = ctx.net
             saved = list(ctx.saved_tensors)
             xyz, idx, widx, xp = saved[:4]
@@ -343,36 +376,17 @@ class PPFNet(nn.Module):
             layers = net._layers()
             B, N, _ = xyz.shape
             K = net.n_sample
-            needs = ctx.needs_input_grad[3:]
             grads = [None] * len(params)
             slot = {id(p): j for j, p in enumerate(net._parameters_in_order())}
+
+            def operand(i):
+                if i == 0:
+                    return ppf_group(xyz, normals, idx).view(B, 10, K * N)
+                return gn_relu(xp if i == _POOLED + 1 else ys[i - 1], affs[2 * i - 2], affs[2 * i - 1])
+
             with on_device_of(xyz):
-                dz = f32c(dout)
-                for i in range(len(layers) - 1, -1, -1):
-                    conv, _ = layers[i]
-                    jw, jb = slot[id(conv.weight)], slot.get(id(conv.bias))
-                    if needs[jw]:
-                        if i == 0:
-                            u = ppf_group(xyz, normals, idx).view(B, 10, K * N)
-                        else:
-                            u = gn_relu(xp if i == _POOLED + 1 else ys[i - 1], affs[2 * i - 2], affs[2 * i - 1])
-                        grads[jw] = wgrad(dz, u).view_as(conv.weight)
-                        del u                              # back to the allocator before du and dz of the layer below are made
-                    if jb is not None and needs[jb]:
-                        grads[jb] = sum_clouds(channel_stats(dz))[:, 0].float()
-                    below = [p for pair in layers[:i] for m in pair for p in (m.weight, m.bias) if p is not None]
-                    if not any(needs[slot[id(p)]] for p in below):
-                        break                              # the first layer, or nothing underneath learns
-                    w = f32c(params[jw]).view(conv.out_channels, conv.in_channels)
-                    du = gn_conv(dz, None, None, w.t().contiguous(), None)[0]
-                    del dz                                 # (the widest one is the pooled layer's [B,C,K N]: gone before the next is made)
-                    norm = layers[i - 1][1]
-                    jg, jt = slot[id(norm.weight)], slot[id(norm.bias)]
-                    pooled = i - 1 == _POOLED
-                    dz, grads[jg], grads[jt] = gn_backward(du, ys[i - 1], affs[2 * i - 2], affs[2 * i - 1], stats[i - 1], params[jg],
-                                                           norm.num_groups, widx if pooled else None, K if pooled else 0,
-                                                           want_gamma=needs[jg], want_beta=needs[jt])
-                    del du
+                backward_descent(layers, ys, affs, stats, params, ctx.needs_input_grad[3:], slot, grads, [f32c(dout)],
+                                 len(layers) - 1, operand, pooled=(_POOLED, widx, K))
             return (None, None, None, *grads)
 
     def forward(self, xyz, normals):

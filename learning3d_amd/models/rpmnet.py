@@ -46,7 +46,7 @@ import torch.nn.functional as F
 from .. import _lib
 from .._lib import call, f32c, on_device_of
 from ..utils import angle_difference, square_distance as _device_square_distance
-from .ppfnet import PPFNet, _device_ops_take, _kernel_takes, _square_distance, gn_affine, gn_backward, gn_conv, gn_mean_rstd, gn_relu
+from .ppfnet import PPFNet, _device_ops_take, _kernel_takes, _square_distance, backward_descent, gn_affine, gn_conv, gn_mean_rstd, gn_relu
 from .ppfnet import op_sequence_only
 from .ppfnet import _TLS as _ppfnet_tls
 from . import _fused
@@ -221,10 +221,8 @@ class ParameterPredictionNet(nn.Module):
         """src [B,J,3], ref [B,K,3] -> the pooled activation [B,1024], differentiable with respect to the 20 pre-pool parameter
         tensors.  forward: fused_prepool's launch list plus an l3d_gn_mean_rstd per layer.  Kept for the backward: the input [B,4,P],
         the convolution outputs y1..y4, per layer a, s [B,C] and (mean, rstd), layer 5's winning extreme and its position [B,1024],
-        the parameters -- no [B,1024,P] tensor.  backward: layer 5 by gn_gpool_backward (its output formed again), then, last layer to
-        first as PPFNet._Train does, dW by l3d_wgrad on the operand l3d_gn_relu writes (released behind the wgrad), db from
-        l3d_channel_stats, du = W^T dz by l3d_gn_conv on the transposed weight, gn_backward dense; it stops at the lowest layer that
-        learns."""
+        the parameters -- no [B,1024,P] tensor.  backward: layer 5's GroupNorm by gn_gpool_backward (its output formed again), then
+        ppfnet.backward_descent from layer 5's convolution, every layer dense; it stops at the lowest layer that learns."""
 
         @staticmethod
         def forward(ctx, net, src, ref, *params):
@@ -237,7 +235,6 @@ class ParameterPredictionNet(nn.Module):
         @staticmethod
         @torch.autograd.function.once_differentiable
         def backward(ctx, dpooled):
-            from ._train import channel_stats, sum_clouds, wgrad
             net = ctx.net
             layers = net._layers()
             L = len(layers)
@@ -247,43 +244,20 @@ class ParameterPredictionNet(nn.Module):
             needs = ctx.needs_input_grad[3:]
             grads = [None] * len(params)
             slot = {id(p): j for j, p in enumerate(net._parameters_in_order())}
-
-            def learns_below(i):
-                """does the convolution of layer i, or anything underneath, need a gradient"""
-                upto = [p for c, n in layers[:i] for p in (c.weight, c.bias, n.weight, n.bias)] + [layers[i][0].weight, layers[i][0].bias]
-                return any(needs[slot[id(p)]] for p in upto)
-
+            conv, norm = layers[-1]
+            jw, jb, jg, jt = (slot[id(p)] for p in (conv.weight, conv.bias, norm.weight, norm.bias))
+            # layer 5's dz is wanted where its convolution, or anything underneath, learns
+            upto = [p for pair in layers[:-1] for m in pair for p in (m.weight, m.bias)] + [conv.weight, conv.bias]
             with on_device_of(x):
-                conv, norm = layers[-1]
-                a5, s5 = affs[-2], affs[-1]
-                g = f32c(dpooled) * (net._pooled(a5, s5, ext) > 0)
-                jg, jt = slot[id(norm.weight)], slot[id(norm.bias)]
-                dz, grads[jg], grads[jt] = gn_gpool_backward(
-                    ys[-1] if L > 1 else x, affs[-4] if L > 1 else None, affs[-3] if L > 1 else None, params[slot[id(conv.weight)]],
-                    params[slot[id(conv.bias)]], g, ext, pw, stats[-1], params[jg], norm.num_groups, want_dz=learns_below(L - 1),
+                g = f32c(dpooled) * (net._pooled(affs[-2], affs[-1], ext) > 0)
+                dz = [None]                                # layer 5's is the one [B,1024,P] tensor: no second reference to it
+                dz[0], grads[jg], grads[jt] = gn_gpool_backward(
+                    ys[-1] if L > 1 else x, affs[-4] if L > 1 else None, affs[-3] if L > 1 else None, params[jw], params[jb], g, ext, pw,
+                    stats[-1], params[jg], norm.num_groups, want_dz=any(needs[slot[id(p)]] for p in upto),
                     want_gamma=needs[jg], want_beta=needs[jt])
-                for i in range(L - 1, -1, -1):
-                    if dz is None:
-                        break
-                    conv, _ = layers[i]
-                    jw, jb = slot[id(conv.weight)], slot[id(conv.bias)]
-                    if needs[jw]:
-                        u = x if i == 0 else gn_relu(ys[i - 1], affs[2 * i - 2], affs[2 * i - 1])
-                        grads[jw] = wgrad(dz, u).view_as(conv.weight)
-                        del u                              # back to the allocator before du and dz of the layer below are made
-                    if needs[jb]:
-                        grads[jb] = sum_clouds(channel_stats(dz))[:, 0].float()
-                    if i == 0 or not (learns_below(i - 1) or needs[slot[id(layers[i - 1][1].weight)]]
-                                      or needs[slot[id(layers[i - 1][1].bias)]]):
-                        break                              # the first layer, or nothing underneath learns
-                    w = f32c(params[jw]).view(conv.out_channels, conv.in_channels)
-                    du = gn_conv(dz, None, None, w.t().contiguous(), None)[0]
-                    del dz                                 # layer 5's is the one [B,1024,P] tensor: gone before the next is made
-                    norm = layers[i - 1][1]
-                    jg, jt = slot[id(norm.weight)], slot[id(norm.bias)]
-                    dz, grads[jg], grads[jt] = gn_backward(du, ys[i - 1], affs[2 * i - 2], affs[2 * i - 1], stats[i - 1], params[jg],
-                                                           norm.num_groups, want_gamma=needs[jg], want_beta=needs[jt])
-                    del du
+                if dz[0] is not None:
+                    backward_descent(layers, ys, affs, stats, params, needs, slot, grads, dz, L - 1,
+                                     lambda i: x if i == 0 else gn_relu(ys[i - 1], affs[2 * i - 2], affs[2 * i - 1]))
             return (None, None, None, *grads)
 
     def forward(self, x):

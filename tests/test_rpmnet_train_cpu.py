@@ -161,6 +161,49 @@ def test_gate_needs_grad_mode_a_parameter_and_the_switch():
     assert not PPFNet(emb_dims=40).trains_on_hip(fake(False), fake(False))
 
 
+@pytest.mark.parametrize("learn,want", [
+    # which of (conv, norm) per layer learn -> the launches, last layer first
+    ([(1, 1), (1, 1), (1, 1)], "w2 b2 d2 n1 w1 b1 d1 n0 w0 b0"),
+    ([(0, 0), (0, 0), (1, 1)], "w2 b2"),                       # nothing underneath learns: no dgrad at all
+    ([(0, 0), (0, 1), (1, 0)], "w2 b2 d2 n1"),                 # only the GroupNorm below: its backward, then stop
+    ([(1, 0), (0, 0), (0, 0)], "d2 n1 d1 n0 w0 b0"),           # only the first convolution: all the way down, no wgrad on the way
+    ([(0, 0), (1, 0), (0, 1)], "d2 n1 w1 b1"),
+])
+def test_backward_descent_stops_where_nothing_underneath_learns(monkeypatch, learn, want):
+    """ppfnet.backward_descent on a three-layer stack with the launches stubbed (a gradient is a tensor holding its layer's number):
+    what runs for each pattern of parameters that need a gradient, which gradients come back, that the list it takes dz in is
+    emptied, and that only the pooled layer's GroupNorm gets the winner index"""
+    from learning3d_amd.models import _train
+    layers = [(torch.nn.Conv1d(4, 4, 1), torch.nn.GroupNorm(2, 4)) for _ in range(3)]
+    order = [p for c, n in layers for p in (c.weight, c.bias, n.weight, n.bias)]
+    slot = {id(p): j for j, p in enumerate(order)}
+    needs = [bool(learn[j // 4][(j % 4) // 2]) for j in range(12)]
+    ran = []
+    at = lambda i: torch.full((1, 4, 1), float(i))                        # noqa: E731
+    log = lambda tag, dz, out: ran.append(f"{tag}{int(dz[0, 0, 0])}") or out       # noqa: E731
+    monkeypatch.setattr(_train, "wgrad", lambda dz, u: log("w", dz, torch.zeros(4, 4)) if u == int(dz[0, 0, 0]) else None)
+    monkeypatch.setattr(_train, "channel_stats", lambda dz: log("b", dz, torch.zeros(1, 4, 2)))
+    monkeypatch.setattr(_train, "sum_clouds", lambda t: t[0])
+    monkeypatch.setattr(ppfnet, "gn_conv", lambda dz, a, s, w, b: (log("d", dz, dz), None, None, None))
+
+    def gn_backward(du, y, a, s, stat, gamma, groups, widx=None, K=0, want_gamma=True, want_beta=True):
+        i = int(du[0, 0, 0]) - 1                                          # du came from the layer above
+        assert (y, a, s, stat) == (f"y{i}", f"a{i}", f"s{i}", f"stat{i}") and gamma is order[4 * i + 2] and groups == 2
+        assert (widx, K) == (("widx", 5) if i == 1 else (None, 0))
+        assert (want_gamma, want_beta) == (needs[4 * i + 2], needs[4 * i + 3])
+        ran.append(f"n{i}")
+        return at(i), at(i) if want_gamma else None, at(i) if want_beta else None
+    monkeypatch.setattr(ppfnet, "gn_backward", gn_backward)
+
+    grads, box = [None] * 12, [at(2)]
+    ys, stats, affs = ["y0", "y1", "y2"], ["stat0", "stat1", "stat2"], ["a0", "s0", "a1", "s1", "a2", "s2"]
+    ppfnet.backward_descent(layers, ys, affs, stats, order, needs, slot, grads, box, 2, lambda i: i, pooled=(1, "widx", 5))
+    assert box == [] and " ".join(ran) == want
+    for j, g in enumerate(grads):
+        i, kind = j // 4, "wbnn"[j % 4]
+        assert (g is not None) == (needs[j] and f"{kind}{i}" in want.split()), (j, g)
+
+
 def test_the_plumbing_case_meets_its_condition_here():
     """the RPMNet pair of the GPU plumbing test: the op sequence's fp32 gradients within 1e-3 of scale of fp64 on every tensor, on
     this machine's CPU, and the fixture's table names every parameter"""
