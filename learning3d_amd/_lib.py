@@ -193,6 +193,47 @@ def stream_ptr():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+class _Built(tuple):
+    """(device index, raw stream, event) of a cache entry.  Entries live in module __dict__s, which copy.deepcopy and pickle walk, and
+    an event can be neither copied nor pickled: a deep copy stands behind the copies of the entry's tensors (made on the current
+    stream just before: the mark is the entry's last element), an unpickled one knows of no build."""
+    __slots__ = ()
+
+    def __deepcopy__(self, memo):
+        if not torch.cuda.is_available() or torch.cuda.is_current_stream_capturing():
+            return _Built((self[0], None, None))
+        event = torch.cuda.Event()
+        event.record(torch.cuda.current_stream(self[0]))
+        return _Built((self[0], torch._C._cuda_getCurrentRawStream(self[0]), event))
+
+    def __reduce__(self):
+        return (_Built, ((self[0], None, None),))
+
+
+def built_on(t):
+    """What a process-wide cache remembers of a device tensor it has just ENQUEUED the build of: (device index, the raw stream the
+    build was put on, an event recorded behind it); None for a host tensor.  Under a capture no event is recorded (an event
+    recorded inside a capture cannot be waited for outside it): a cache filled during a capture orders nothing across streams."""
+    if t is None or not t.is_cuda:
+        return None
+    index = t.get_device()
+    raw = torch._C._cuda_getCurrentRawStream(index)
+    if torch.cuda.is_current_stream_capturing():
+        return _Built((index, raw, None))
+    event = torch.cuda.Event()
+    event.record(torch.cuda.current_stream(index))
+    return _Built((index, raw, event))
+
+
+def order_after_build(mark):
+    """A cache hit: on the stream the entry was built on, one comparison and nothing else -- no event call, no launch.  On any other
+    stream the current stream waits for the build (the tensor was enqueued there, not necessarily written yet); while capturing it
+    does not (a wait on an outside event would enter the graph: warm up on the capture's stream, or join, before capturing)."""
+    if mark is not None and torch._C._cuda_getCurrentRawStream(mark[0]) != mark[1]:
+        if mark[2] is not None and not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream(mark[0]).wait_event(mark[2])
+
+
 def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 

@@ -426,7 +426,7 @@ __global__ __launch_bounds__(256) void at_absmax3_kernel(const float *__restrict
 static int l3d_attention_absmax3(const float *q, const float *k, const float *v, long q_bs, long k_bs, long v_bs, long q_span, long kv_span,
                                  int B, unsigned *amax, hipStream_t st)
 {
-    if (hipMemsetAsync(amax, 0, 16, st) != hipSuccess) return L3D_ERR_LAUNCH;
+    if (l3d_zero_async(amax, 16, st) != hipSuccess) return L3D_ERR_LAUNCH;
     hipLaunchKernelGGL(at_absmax3_kernel, dim3(512, 3), dim3(256), 0, st, q, k, v, q_bs, k_bs, v_bs, q_span, kv_span, B, amax);
     return l3d_check_launch();
 }

@@ -51,6 +51,26 @@ __device__ __forceinline__ double l3d_block_sum(double v, double *sRed)
     return ((sRed[0] + sRed[1]) + sRed[2]) + sRed[3];
 }
 
+// Zero `bytes` bytes (a multiple of 4, dst 4-byte aligned) on stream st, as a kernel.  Not hipMemsetAsync: captured into a graph, a
+// memset did not do on replay what it does when issued eagerly -- every entry point that used one replayed other bits than it
+// computes eagerly, and l3d_scatter_add_det walked off its workspace on counters that had not been cleared
+// (tests/test_gpu_streams_abi.py).  A kernel node is ordered on replay like every other launch of the entry point.
+#ifdef __HIPCC__
+static __global__ __launch_bounds__(256) void l3d_zero_kernel(uint32_t *__restrict__ p, size_t words)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) p[i] = 0u;
+}
+
+static inline hipError_t l3d_zero_async(void *dst, size_t bytes, hipStream_t st)
+{
+    const size_t words = bytes / 4;
+    if (words == 0) return hipSuccess;
+    const size_t blocks = (words + 255) / 256;
+    hipLaunchKernelGGL(l3d_zero_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, (uint32_t *)dst, words);
+    return hipGetLastError();
+}
+#endif
+
 // sizes of the f16x2 plane images (conv_f16.hip; exported as l3d_f16_image_bytes(kind, rows, cols))
 static inline size_t l3d_f16_plane_bytes(long rows, int cols) { return (size_t)((cols + 7) / 8) * (size_t)rows * 16; }   // one plane, tiled layout
 static inline size_t l3d_f16_act_bytes(long rows, int cols) { return 2 * l3d_f16_plane_bytes(rows, cols) + 16; }         // h | m' + {2^-T, scratch}

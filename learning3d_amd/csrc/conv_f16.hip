@@ -921,7 +921,7 @@ extern "C" int l3d_conv_f16_split_weights(const float *w, int Cout, int Cin, voi
     float *rinv = (float *)(d + 3 * pb + 16);
     // the image's 16 bytes behind the planes: (unused) | (unused) | row-sum maximum | (unused).  All four are zeroed: the header
     // promises a fully written image, and the two outer words were left as the allocation held them (nothing reads them)
-    if (hipMemsetAsync(d + 3 * pb, 0, 16, st) != hipSuccess) return L3D_ERR_LAUNCH;
+    if (l3d_zero_async(d + 3 * pb, 16, st) != hipSuccess) return L3D_ERR_LAUNCH;
     hipLaunchKernelGGL(cf_rowsum_kernel, dim3((unsigned)l3d_divup(Cout, 4)), dim3(256), 0, st, w, Cout, Cin, amax + 1, rinv);
     const long cells = (long)Cout * ((Cin + 7) / 8);
     hipLaunchKernelGGL(cf_split_w_kernel, dim3((unsigned)l3d_divup(cells, 256)), dim3(256), 0, st, w, Cout, Cin, (const float *)rinv,
@@ -940,7 +940,7 @@ extern "C" int l3d_split_f16_rows(const float *x, long rows, int C, int channel_
     unsigned char *d = (unsigned char *)dst;
     float *inv = (float *)(d + 2 * pb);
     unsigned *amax = (unsigned *)(d + 2 * pb + 4);
-    if (hipMemsetAsync(amax, 0, 4, st) != hipSuccess) return L3D_ERR_LAUNCH;
+    if (l3d_zero_async(amax, 4, st) != hipSuccess) return L3D_ERR_LAUNCH;
     const size_t n = (size_t)rows * C;
     const long nblk = l3d_divup((long)n, 4096);
     hipLaunchKernelGGL(cf_absmax_kernel, dim3((unsigned)(nblk > 2048 ? 2048 : nblk)), dim3(256), 0, st, x, n, amax);
@@ -971,7 +971,7 @@ extern "C" int l3d_split_f16_operand(const float *x, long rows, int C, long row_
     uint4 *ph = (uint4 *)d, *pm = (uint4 *)(d + (kind ? 2 : 1) * pb);
     float *inv = (float *)(d + (kind ? 3 : 2) * pb);
     unsigned *amax = (unsigned *)(inv + 1);
-    if (hipMemsetAsync(inv, 0, 16, st) != hipSuccess) return L3D_ERR_LAUNCH;
+    if (l3d_zero_async(inv, 16, st) != hipSuccess) return L3D_ERR_LAUNCH;
     float *rinv = kind ? inv + 4 : nullptr;
     if (kind) {
         hipLaunchKernelGGL(cf_rowinv_act_kernel, dim3((unsigned)l3d_divup(rows, 4L)), dim3(256), 0, st, x, rows, C, row_stride, rinv);

@@ -658,7 +658,7 @@ static int launch_group(bool grad, int b, int c, int n, int total, const float *
 {
     dim3 grid(l3d_divup(total, 256), l3d_divup(c, GP_CCHUNK), b);
     if (grad) {
-        hipError_t e = hipMemsetAsync(dst, 0, sizeof(float) * (size_t)b * c * n, st);
+        hipError_t e = l3d_zero_async(dst, sizeof(float) * (size_t)b * c * n, st);
         if (e != hipSuccess) { g_l3d_last_hip_error = (int)e; return L3D_ERR_LAUNCH; }
         hipLaunchKernelGGL(group_points_grad_kernel, grid, dim3(256), 0, st, c, n, total, src, idx, dst);
     } else {
@@ -1119,7 +1119,7 @@ extern "C" int l3d_three_interpolate_grad(int b, int c, int n, int m, const floa
 {
     L3D_REQUIRE(grad_out && idx && weight && grad_points && b > 0 && c > 0 && m > 0 && n > 0);
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(grad_points, 0, sizeof(float) * (size_t)b * c * m, st);
+    hipError_t e = l3d_zero_async(grad_points, sizeof(float) * (size_t)b * c * m, st);
     if (e != hipSuccess) { g_l3d_last_hip_error = (int)e; return L3D_ERR_LAUNCH; }
     hipLaunchKernelGGL(three_interpolate_grad_kernel,
                        dim3(l3d_divup(n, 256), l3d_divup(c, GP_CCHUNK), b), dim3(256), 0, st, c, n, m,

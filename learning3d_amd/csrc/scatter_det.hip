@@ -257,7 +257,7 @@ extern "C" int l3d_scatter_add_det(const float *src, const int32_t *idx, const f
     uint32_t *order = (uint32_t *)w;
     unsigned *counts = (unsigned *)(w + seg);
     uint32_t *start = (uint32_t *)(w + seg + tseg);
-    if (hipMemsetAsync(counts, 0, (size_t)slots * 4, st) != hipSuccess) return L3D_ERR_LAUNCH;
+    if (l3d_zero_async(counts, (size_t)slots * 4, st) != hipSuccess) return L3D_ERR_LAUNCH;
     hipLaunchKernelGGL(sd_count_kernel, dim3(l3d_divup(total, 256)), dim3(256), 0, st, idx, E, T, R, rlen, total, counts);
     hipLaunchKernelGGL(sd_scan_kernel, dim3(B), dim3(1024), 0, st, counts, T * R, E, B, start);
     hipLaunchKernelGGL(sd_place_sorted_kernel, dim3(R, B), dim3(1024), 0, st, idx, E, T, R, rlen, counts, (const uint32_t *)start, order);

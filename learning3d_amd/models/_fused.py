@@ -16,7 +16,8 @@ import threading
 
 import torch
 
-from .._lib import L3D_CONV_F16_OUT_UNSCALED, L3D_CONV_F16_TWO_PLANE, call, f32a, f32c, lib, ptr, require_gpu
+from .._lib import (L3D_CONV_F16_OUT_UNSCALED, L3D_CONV_F16_TWO_PLANE, built_on, call, f32a, f32c, lib, order_after_build, ptr,
+                    require_gpu)
 
 
 class _NullSpan:
@@ -99,13 +100,16 @@ def cached(store, name, sources, build, extra=()):
     The entry keeps the sources' storage alive (detached aliases), as _OBS_CACHE does: otherwise a freed block could come back
     under the same key with other values in it -- `module.half().float()` swaps every param.data and keeps its version, and a
     derived tensor (a folded weight or scale) is freed when its own cache is rebuilt.  Edits through `param.data` bump no version
-    and are not seen."""
+    and are not seen.
+    The entry also remembers the stream its build was enqueued on and an event behind it: a hit from another stream waits for that
+    event, a hit from the same stream costs one comparison (_lib.order_after_build)."""
     key = tuple(extra) + state_key(sources)
     hit = store.get(name)
     if hit is not None and hit[0] == key:
+        order_after_build(hit[3])
         return hit[1]
     out = build()
-    store[name] = (key, out, [t.detach() for t in sources if t is not None])
+    store[name] = (key, out, [t.detach() for t in sources if t is not None], built_on(next((t for t in sources if t is not None), None)))
     return out
 
 
@@ -365,8 +369,9 @@ def _plane_obs(scale, shift, dev):
         hit = torch.stack([shift.abs().max() if shift is not None else torch.zeros((), device=dev),
                            scale.abs().max() if scale is not None else torch.ones((), device=dev)]).float()
         # keep the keyed tensors alive with the entry: a freed tensor's address could be handed to another parameter
-        _OBS_CACHE[key] = (hit, scale, shift)
+        _OBS_CACHE[key] = (hit, scale, shift, built_on(hit))
         return hit
+    order_after_build(hit[3])
     return hit[0]
 
 

@@ -13,19 +13,22 @@ import os
 import torch
 
 from .._lib import (L3D_BMM_ROUTE_A_SHIFT, L3D_BMM_ROUTE_B_SHIFT, L3D_BMM_ROUTE_REMAPPED, L3D_BMM_ROUTE_YT_MASK, L3D_CONV_F16_SHIFT_N,
-                    L3D_CONV_F16_TWO_PLANE, call, check, f32c, lib, on_device_of, ptr)
+                    L3D_CONV_F16_TWO_PLANE, built_on, call, check, f32c, lib, on_device_of, order_after_build, ptr)
 
 _ONES = {}
 
 
 def _ones(n, dev):
     key = (n, str(dev))
-    t = _ONES.get(key)
-    if t is None:
+    hit = _ONES.get(key)
+    if hit is None:
         if len(_ONES) > 32:
             _ONES.clear()
-        t = _ONES[key] = torch.ones(n, dtype=torch.float32, device=dev)
-    return t
+        t = torch.ones(n, dtype=torch.float32, device=dev)
+        hit = _ONES[key] = (t, built_on(t))
+    else:
+        order_after_build(hit[1])
+    return hit[0]
 
 
 def _as4(t):
@@ -200,9 +203,10 @@ def _row_operand(x):
     key = (x.data_ptr(), x._version, tuple(x.shape), tuple(x.stride()), str(x.device))
     hit = _A_IMG.get("last")
     if hit is not None and hit[0] == key:
+        order_after_build(hit[3])
         return hit[2]
     img = _operand(x, 1)
-    _A_IMG["last"] = (key, x, img)
+    _A_IMG["last"] = (key, x, img, built_on(img))
     return img
 
 

@@ -27,7 +27,8 @@ def transform_point_cloud(point_cloud, rotation, translation):
 def convert2transformation(rotation_matrix, translation_vector):
     """ops/transform_functions.py:31-35."""
     B = rotation_matrix.shape[0]
-    bottom = torch.tensor([[[0.0, 0.0, 0.0, 1.0]]]).repeat(B, 1, 1).to(rotation_matrix)
+    bottom = rotation_matrix.new_zeros((B, 1, 4))        # built where the rotation lives: a host tensor copied over cannot be captured
+    bottom[:, :, 3] = 1.0
     top = torch.cat([rotation_matrix, translation_vector.unsqueeze(-1)], dim=2)
     return torch.cat([top, bottom], dim=1)
 

@@ -35,9 +35,12 @@ CHANNEL_FIRST_PASS = True   # a whole encoder-decoder pass in the [B,C,N] layout
 _ATT_WS = {}
 
 
-def _attention_workspace(device):
-    """16 bytes per device for l3d_attention_forward_f16b's operand maxima (written and read on the launch stream)."""
-    key = str(device)
+def _attention_workspace(device, stream=None):
+    """16 bytes per device AND stream for l3d_attention_forward_f16b's operand maxima (written and read on the launch stream: two
+    streams sharing them would overwrite each other's).  stream: the raw stream handle, the device's current one by default."""
+    if stream is None:
+        stream = torch.cuda.current_stream(device).cuda_stream
+    key = (str(device), stream)
     ws = _ATT_WS.get(key)
     if ws is None:
         ws = torch.zeros(4, dtype=torch.int32, device=device)

@@ -28,6 +28,15 @@ class ContractError(AssertionError):
     """a launch broke the memory contract of its entry point"""
 
 
+# Hooks for a second way of running the same cases (tests/golden/stream_cases.py sets and resets them, a context manager each):
+# DEFAULT_LAUNCH: what check() launches through when a case passes no `launch` (None: `_lib.call`).  ACTIVE is, for the time of one
+# check(), what such a launch needs besides its arguments: (name, proto, contract, sizefn).
+# RECORD: a list to which check() appends (name, values, {parameter: (clone of the tensor, spec)}) of its fill-B run.
+DEFAULT_LAUNCH = None
+ACTIVE = None
+RECORD = None
+
+
 # One writable parameter.  kind: "written" | "inout" | "scratch".  size: None, or (size function, args(v) -> tuple, bytes per unit)
 # with v = {parameter name: the call's argument}; a size function given as a callable is called as it is (the ball-query formula).
 # keep: bytes at the front of a scratch area that carry state from call to call ("zero before the first call, the kernel re-arms
@@ -336,14 +345,55 @@ def _run(name, proto, build, launch, arena, contract, sizefn):
     return values, writable
 
 
+def compare_runs(name, values, what1, w1, what2, w2):
+    """(c) of the module text for two runs of one call: w1, w2 = [(parameter, tensor, spec)] of its writable tensors"""
+    by_name = {pname: a for pname, a, _ in w2}
+    count = by_name.get("count")
+    for pname, a, spec in w1:
+        if spec.kind == "scratch":
+            continue
+        b = by_name[pname]
+        nbytes = a.numel() * a.element_size()
+        if spec.open is None:
+            open_ranges = []
+        elif name == "l3d_mask_select":
+            open_ranges = spec.open(values, nbytes, None if count is None else int(count.reshape(-1)[0]))
+        else:
+            open_ranges = spec.open(values, nbytes)
+        if spec.bound is not None:
+            assert spec.quote, f"{name}: a tolerance for `{pname}` must quote the header line that makes it order-dependent"
+            bar = spec.bound(values)
+            ok = (a.double() - b.double()).abs() <= bar          # (a NaN, an element never written under fill A, is not <= anything)
+            if not bool(ok.all()):
+                at = int((~ok).reshape(-1).nonzero()[0]) * a.element_size()
+                raise ContractError(f"{name}: parameter `{pname}` differs beyond its summation bound at byte offset {at} of {nbytes} "
+                                    f"between {what1} and {what2}")
+            continue
+        at = _first_difference(a, b, open_ranges)
+        if at is not None:
+            raise ContractError(f"{name}: parameter `{pname}` ({spec.kind}) differs at byte offset {at} of {nbytes} between {what1} and "
+                                f"{what2}: an element that was not written, or a result that depends on what the memory held")
+
+
 def check(name, build, launch=None, contract=None, proto=None, sizefn=None, device="cuda"):
     """Run entry point `name` with the arguments build(arena) under fill A and under fill B (and, where a workspace carries state from
     call to call, a third time on the workspace the second run left) and hold it to (a), (b), (c) of the module text.
     -> the writable tensors of the fill-B run, {parameter: tensor}: the values a case goes on to compare with its reference."""
-    if launch is None:
+    global ACTIVE
+    if launch is None and DEFAULT_LAUNCH is not None:
+        launch = DEFAULT_LAUNCH
+    elif launch is None:
         from learning3d_amd import _lib
         launch = _lib.call
     proto = proto or prototypes()[name]
+    ACTIVE, outer = (name, proto, contract, sizefn), ACTIVE
+    try:
+        return _check(name, build, launch, contract, proto, sizefn, device)
+    finally:
+        ACTIVE = outer
+
+
+def _check(name, build, launch, contract, proto, sizefn, device):
     runs = []
     for label, fill in FILLS:
         arena = Arena(fill, device)
@@ -355,32 +405,9 @@ def check(name, build, launch=None, contract=None, proto=None, sizefn=None, devi
         _, wc = _run(name, proto, build, launch, arena_c, contract, sizefn)
         compare.append(("a second call on the workspace the first left", wc, "the first call", wb))
     for what1, w1, what2, w2 in compare:
-        by_name = {p.name: a for p, a, _ in w2}
-        count = by_name.get("count")
-        for p, a, spec in w1:
-            if spec.kind == "scratch":
-                continue
-            b = by_name[p.name]
-            nbytes = a.numel() * a.element_size()
-            if spec.open is None:
-                open_ranges = []
-            elif name == "l3d_mask_select":
-                open_ranges = spec.open(values, nbytes, None if count is None else int(count.reshape(-1)[0]))
-            else:
-                open_ranges = spec.open(values, nbytes)
-            if spec.bound is not None:
-                assert spec.quote, f"{name}: a tolerance for `{p.name}` must quote the header line that makes it order-dependent"
-                bar = spec.bound(values)
-                ok = (a.double() - b.double()).abs() <= bar          # (a NaN, an element never written under fill A, is not <= anything)
-                if not bool(ok.all()):
-                    at = int((~ok).reshape(-1).nonzero()[0]) * a.element_size()
-                    raise ContractError(f"{name}: parameter `{p.name}` differs beyond its summation bound at byte offset {at} of {nbytes} "
-                                        f"between {what1} and {what2}")
-                continue
-            at = _first_difference(a, b, open_ranges)
-            if at is not None:
-                raise ContractError(f"{name}: parameter `{p.name}` ({spec.kind}) differs at byte offset {at} of {nbytes} between {what1} and "
-                                    f"{what2}: an element that was not written, or a result that depends on what the memory held")
+        compare_runs(name, values, what1, [(p.name, a, spec) for p, a, spec in w1], what2, [(p.name, a, spec) for p, a, spec in w2])
+    if RECORD is not None:
+        RECORD.append((name, values, {p.name: (a.clone(), spec) for p, a, spec in wb}))
     return {p.name: a for p, a, _ in wb}
 
 
