@@ -255,11 +255,12 @@ def test_first_layer_f16_planes_per_channel(kind):
     _fused.check_range(sync=True)
 
 
-@pytest.mark.parametrize("kind", ["spread", "tiny"])
+@pytest.mark.parametrize("kind", ["spread", "tiny", "offset"])
 def test_group_first_layer_planes_per_channel(kind):
     """l3d_group_first_layer_planes_auto (FlowNet3D's factored first layer, act(U[idx] + shift + Wx (xyz[idx] - centre)) as an activation
-    image): U channels x 10^U(-4, 0), Wx rows x 10^U(-4, 0); 'tiny': every input 1e-36, no shift.  Per channel against fp64 and the fp32
-    kernel (l3d_group_first_layer)."""
+    image): U channels x 10^U(-4, 0), Wx rows x 10^U(-4, 0); 'tiny': every input 1e-36, no shift; 'offset': points and centres moved by
+    (1000, -50, 3), so the image's scale, taken from max|xyz| + max|new_xyz|, is a thousand times the coordinate differences it holds
+    (the bar follows that scale through oinv).  Per channel against fp64 and the fp32 kernel (l3d_group_first_layer)."""
     from learning3d_amd._lib import check, lib, ptr, stream_ptr
     from learning3d_amd.models import _fused
     rng = np.random.default_rng(130 + len(kind))
@@ -269,6 +270,8 @@ def test_group_first_layer_planes_per_channel(kind):
     wx = (rng.standard_normal((C1, 3)) * 10.0 ** rng.uniform(-4, 0, (C1, 1))).astype(np.float32)
     sh = np.zeros(C1, np.float32) if kind == "tiny" else (rng.standard_normal(C1) * 1e-3).astype(np.float32)
     xyz = (rng.uniform(-1, 1, (B, N, 3)) * f).astype(np.float32)
+    if kind == "offset":
+        xyz = xyz + np.array([1000.0, -50.0, 3.0], np.float32)
     ctr = xyz[:, :S].copy()
     idx = rng.integers(0, N, (B, S, K)).astype(np.int32)
     Ud, wxd, shd, xd, cd, idd = dev(U), dev(wx), dev(sh), dev(xyz), dev(ctr), dev(idx)
